@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — LM iterations/s and ms per graph solve on the 200-keyframe x 50k-landmark VIO window.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 One "step" = one full graph solve (bsgpu_solve) of BASELINE.json config 2 — the 200 KF x 50 k
 landmark synthetic visual-inertial window of SURVEY.md §8d — from its device-resident initial guess
@@ -14,11 +14,18 @@ N > 1: one process per GPU (launched by torch.distributed.run); every rank solve
 independent window (BASELINE config 5: seeds +10 + rank) — the path shards by window, there is no
 data-path collective; torch.distributed (RCCL) is used for the barriers and the max-over-ranks.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes their outputs if --dump-outputs asks for them and prints the line.
+
+--dump-outputs DIR: after the timed steps, what the last one computed goes to DIR/<name>.npy (float64): parameters (the solved values
+of every window's blocks, a fixed seeded sample above 56 MB), iteration_cost (the cost of every recorded LM iteration) and summary
+(one row per window: SUMMARY_FIELDS).  Ranks > 0 of an N-GPU run write under DIR/rank<r>/.
+
+--full also measures what the headline does not need, and the JSON line then also carries
   roofline     — the reprojection Jacobian-evaluation kernel: algorithmic bytes / HIP-event time measured in situ (inside real LM
                  steps), plus the same kernel on a working set above the 256 MiB Infinity Cache (past_l3)
   roofline_mfma, kernels, phases_us_per_lm_step — the Cholesky of the reduced camera system against the FP64 MFMA peak, the other
                  HBM-bound kernels of a step, and where an LM step's time goes (bsgpu_profile_step)
+  sustained, other_configs — back-to-back solves of the headline window; C3, C4, batches of windows and the host cycle, a few steps each
   cpu_baseline — the CPU oracle (own restatement, kind "port") on the same window, rank 0, N=1
 """
 import argparse
@@ -36,6 +43,21 @@ PROFILE_ROUND = "r06"      # profiles/<round>_*_pmc_hbm.csv: the PMC passes `tra
 MFMA_F64_PEAK_TF = 78.6    # ... dense FP64 MFMA (v_mfma_f64_16x16x4_f64: 64 cycles / instruction / SIMD)
 MFMA_NOTE = ("latency-bound, not MFMA-bound: the critical path is the pivot chain of the chains on it (a leaf piece + one separator per "
              "level, 16 pivots at a time inside one workgroup: chol_chain.h) plus one hand-over per level; DESIGN.md 3.2")
+SUMMARY_FIELDS = ("initial_cost", "final_cost", "num_iterations", "num_successful_steps", "num_unsuccessful_steps", "num_linear_solves",
+                  "num_inner_iterations", "termination_type", "is_solution_usable")
+DUMP_MAX_VALUES = 7 * 1024 * 1024   # parameters.npy above this many float64 values (56 MB): a fixed seeded sample of them
+
+
+def dump_outputs(dirname, solvers, summaries):
+    """What the last timed step handed back, read from the solvers' contexts (no further device work)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    x = np.concatenate([g.get_blocks() for g in solvers])
+    if x.size > DUMP_MAX_VALUES:
+        x = x[np.sort(np.random.default_rng(0).choice(x.size, DUMP_MAX_VALUES, replace=False))]
+    np.save(os.path.join(dirname, "parameters.npy"), x.astype(np.float64))
+    np.save(os.path.join(dirname, "iteration_cost.npy"), np.array([it.cost for g in solvers for it in g.iterations()], np.float64))
+    np.save(os.path.join(dirname, "summary.npy"), np.array([[float(getattr(s, f)) for f in SUMMARY_FIELDS] for s in summaries], np.float64))
 
 
 def _attach_traffic(roofline, csv_name, kernel_prefix, nbytes, check_bytes=True):
@@ -62,7 +84,7 @@ def _attach_traffic(roofline, csv_name, kernel_prefix, nbytes, check_bytes=True)
 
 
 def short_leg(which, device):
-    """C3 / C4 for a few steps inside the default run (the driver times them with everything else): same step definition as the
+    """C3 / C4 for a few steps inside the --full run: same step definition as the
     headline — full solves from the device-resident initial guess, the reference's options for that path — plus the roofline of
     the configuration's Jacobian evaluation (relative-pose factors: SURVEY.md 8(d))."""
     from beam_slam_amd import synthetic
@@ -210,6 +232,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the rooflines and phases, the sustained loop, the other configurations and the CPU baseline "
+                         "(the --no-* and --sustained-seconds options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (parameters, iteration_cost, summary)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--n-kf", type=int, default=200)
     ap.add_argument("--n-lm", type=int, default=50000)
@@ -218,7 +245,7 @@ def main():
     ap.add_argument("--workload", default="c2", choices=["c2", "c3", "c4"],
                     help="c2 (default) is the headline; c3 / c4 are the other BASELINE configs, for BASELINE.md")
     ap.add_argument("--no-other-configs", dest="other_configs", action="store_false",
-                    help="skip the short C3 and C4 legs the default (C2, one GPU) run appends under \"other_configs\"")
+                    help="skip the short C3 and C4 legs the --full (C2, one GPU) run appends under \"other_configs\"")
     ap.add_argument("--sustained-seconds", type=float, default=2.5,
                     help="after the timed region: back-to-back C2 solves for this long (\"sustained\"; 0 = skip)")
     ap.add_argument("--windows-per-gpu", type=int, default=0,
@@ -304,6 +331,7 @@ def main():
             torch.cuda.synchronize()
 
     cons = None
+    batch_sums = []   # the windows' own summaries of the last bsgpu_solve_batch
     if args.consensus:
         import numpy as np
         opt.function_tolerance = 1e-12; opt.gradient_tolerance = 1e-12; opt.parameter_tolerance = 1e-12   # (the rounds cannot agree better than the windows are solved)
@@ -342,7 +370,8 @@ def main():
         if wins is not None:
             for gw in wins: gw.reset_values()
             sums = GpuSolver.solve_batch(wins, opt)
-            sm = sums[0]
+            batch_sums[:] = sums
+            sm = type(sums[0]).from_buffer_copy(sums[0])
             sm.num_linear_solves = sum(x.num_linear_solves for x in sums)
             return sm
         g.reset_values()
@@ -360,6 +389,9 @@ def main():
         dev_s += s.device_time_in_seconds
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs if rank == 0 else os.path.join(args.dump_outputs, "rank%d" % rank),
+                     wins if wins is not None else [g], batch_sums if wins is not None else [s])
 
     tot_it, max_dt = float(n_it), dt
     ranks_seen, per_rank = 1, [round(n_it / dt, 2)]
@@ -376,7 +408,7 @@ def main():
         # (bsgpu_profile_step); the kernel-trace average of the same kernels is in profiles/r02_*_kernel_stats.csv
         has_vis = pr.n_factors(0) > 0 and not args.consensus and wins is None
         roofline = roofline_mfma = kernels = phases = None
-        if args.workload in ("c3", "c4"):
+        if args.full and args.workload in ("c3", "c4"):
             # no reprojection factors: the roofline is that of the relative-pose evaluation (~990 B per factor),
             # timed with HIP events on the solver's stream (20 back-to-back evaluations of every factor type of the window)
             ms_e, nb_e = g.time_eval_ms(20), g.eval_bytes()
@@ -388,7 +420,7 @@ def main():
                         "timing": "20 back-to-back evaluations (residuals + Jacobians of every factor type) between two HIP events on the solver's stream",
                         "working_set_mb": round(nb_e / 1e6, 1), "cache_residency": "below the 256 MiB Infinity Cache", "traffic": None}
             _attach_traffic(roofline, "%s_%s_pmc_hbm.csv" % (PROFILE_ROUND, args.workload), rel_kernel + "<true", nb_e)
-        if args.workload == "c3":          # dense Schur path without landmarks: phases and the factorisation's figure
+        if args.full and args.workload == "c3":          # dense Schur path without landmarks: phases and the factorisation's figure
             prof = g.profile_step(opt, reps=20)
             phases = {k: round(1e3 * v[0], 2) for k, v in prof.items()}
             ms_f, flops = prof["factor"]
@@ -403,7 +435,7 @@ def main():
             pcg = {"block_rows": nbr, "nnz_blocks_3x3": nnzb, "bytes_per_inner_iteration": int(it_bytes),
                    "inner_iterations_per_solve": int(s.num_inner_iterations),
                    "note": "pcg_persistent_kernel keeps its blocks in registers: an inner iteration is latency (two cross-XCD reductions), not bandwidth"}
-        if has_vis and not (args.workload == "c4"):
+        if args.full and has_vis and not (args.workload == "c4"):
             prof = g.profile_step(opt, reps=20)
             phases = {k: round(1e3 * v[0], 2) for k, v in prof.items()}          # microseconds per LM step
             ms, nbytes = prof["eval_reproj"]
@@ -481,8 +513,9 @@ def main():
                        "device_ms_per_solve": round(1e3 * dev_s / args.steps, 3),
                        "parallelism": ("%d window%s per GPU, no collective" % (max(1, args.windows_per_gpu), "s" if args.windows_per_gpu > 1 else "")) if (world > 1 or wins is not None) else "single GPU",
                        "n_ranks_seen": ranks_seen, "per_rank_lm_iterations_per_s": per_rank},
-            "roofline": roofline,
         }
+        if args.full:
+            out["roofline"] = roofline
         if phases and not roofline_mfma:
             out["phases_us_per_lm_step"] = phases
         if roofline_mfma:
@@ -503,7 +536,7 @@ def main():
         default_c2 = world == 1 and args.workload == "c2" and not args.consensus and wins is None
         # ---- sustained: back-to-back solves of the same window for a few seconds (the timed region above is 0.1 s of GPU work: too
         # short for an external utilisation sampler to see; this is the same loop, longer)
-        if default_c2 and args.sustained_seconds > 0:
+        if args.full and default_c2 and args.sustained_seconds > 0:
             t1 = time.perf_counter()
             n_s, it_s = 0, 0
             while time.perf_counter() - t1 < args.sustained_seconds:
@@ -514,7 +547,7 @@ def main():
             out["sustained"] = {"seconds": round(dt_s, 2), "solves": n_s, "value": round(it_s / dt_s, 2), "unit": "LM iterations/s",
                                 "note": "back-to-back solves of the headline window after the timed region, same options"}
         # ---- the other single-GPU configurations of BASELINE.json, a few steps each (their own full runs: --workload c3 / c4)
-        if default_c2 and args.other_configs:
+        if args.full and default_c2 and args.other_configs:
             g.close()
             out["other_configs"] = {"c3": short_leg("c3", local_rank), "c4": short_leg("c4", local_rank)}
             # several windows per GPU (what an N-GPU run multiplies): 8 C2-shaped windows — config 5 folded onto one device — and 32 windows of
@@ -538,7 +571,7 @@ def main():
             out["other_configs"]["host_cycle"] = host_cycle_leg()
         # ---- CPU baseline: the oracle on the same window (bounded samples, same options): with every usable core, and with the six
         # threads the reference's own configuration gives Ceres (beam_slam_launch/config/vio.yaml:11 num_threads: 6)
-        if world == 1 and not args.no_cpu_baseline and args.workload != "c4" and not args.consensus and wins is None:   # (C4 at full size: the oracle's dense solve does not finish in bench time)
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload != "c4" and not args.consensus and wins is None:   # (C4 at full size: the oracle's dense solve does not finish in bench time)
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             from oracle import Oracle, usable_cpus
 

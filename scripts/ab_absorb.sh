@@ -1,5 +1,5 @@
 # A/B of the dissection's separator absorption and hand-over constant on one box: bash scripts/ab_absorb.sh
-run() { python bench.py --workload $1 --steps 15 --warmup 3 --no-cpu-baseline --no-past-l3 --no-other-configs --sustained-seconds 0 2>/dev/null | python -c "
+run() { python bench.py --full --workload $1 --steps 15 --warmup 3 --no-cpu-baseline --no-past-l3 --no-other-configs --sustained-seconds 0 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of the factorisation's plan knobs on C2 / C3 (one line per setting): bash scripts/ab_chol.sh
-B="python bench.py --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0"
+B="python bench.py --full --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0"
 ex() { python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

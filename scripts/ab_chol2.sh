@@ -1,4 +1,4 @@
-B="python bench.py --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0"
+B="python bench.py --full --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0"
 ex() { python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

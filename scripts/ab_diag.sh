@@ -1,5 +1,5 @@
 # A/B: the LM diagonal and the gradient norms as tasks of the factorisation's launch (default) against their own launch (BSGPU_POSE_DIAG_LAUNCH=1)
-B="python bench.py --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0"
+B="python bench.py --full --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0"
 ex() { python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the dissection's cost model (dim_order.h: t_chain0, t_hop, t_hop_tile) swept: C2, C3, the small windows, a lidar-inertial window, a pose graph per setting
 #   bash scripts/ab_dim_model.sh "5 10 4" "3 9 8" ...
-B="timeout 300 python bench.py --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0"
+B="timeout 300 python bench.py --full --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0"
 ex() { python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

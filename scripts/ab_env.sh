@@ -1,6 +1,6 @@
 #!/bin/bash
 # one bench line per workload (C2, C3, the reference-sized window), twice:  bash scripts/ab_env.sh [label]
-B="timeout 300 python bench.py --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0"
+B="timeout 300 python bench.py --full --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0"
 ex() { python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

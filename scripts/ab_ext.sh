@@ -1,5 +1,5 @@
 # A/B: appendix tiles carried by the panel before them (BSGPU_CHOL_EXT, default on) against a panel of their own (=0)
-B="python bench.py --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0"
+B="python bench.py --full --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0"
 ex() { python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the factorisation's updates with turns (BSGPU_CHOL_NOTURN=0) / as unordered atomic adds (default): bench lines of C2, C3 and the small window, one box
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"; cd "$ROOT"
-B="timeout 300 python bench.py --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0 --steps 30"
+B="timeout 300 python bench.py --full --no-cpu-baseline --no-other-configs --no-past-l3 --sustained-seconds 0 --steps 30"
 ex() { python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); p=d.get('phases_us_per_lm_step') or {}

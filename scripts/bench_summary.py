@@ -1,4 +1,4 @@
-"""One screen of a default bench line:  python bench.py > b.json; python scripts/bench_summary.py b.json"""
+"""One screen of a full bench line:  python bench.py --full > b.json; python scripts/bench_summary.py b.json"""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print("C2", d["value"], "LM it/s,", d["ms_per_step"], "ms per solve; roofline frac", d["roofline"]["frac"], "sustained", (d.get("sustained") or {}).get("value"))

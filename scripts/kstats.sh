@@ -4,7 +4,7 @@ W=${1:-c2}; N=${2:-12}
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/ks_$W
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$W -o p -- python "$ROOT/bench.py" --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-past-l3 > /tmp/ks_$W.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$W -o p -- python "$ROOT/bench.py" --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-past-l3 > /tmp/ks_$W.log 2>&1
 f=$(find /tmp/ks_$W -name "*kernel_stats.csv" | head -1)
 python - "$f" "$N" <<'PY'
 import csv, sys

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 i=0
 for grp in "$@"; do
   i=$((i+1)); rm -rf /tmp/pk_$i
-  timeout 400 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d /tmp/pk_$i -o p -- python "$ROOT/bench.py" --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-past-l3 > /tmp/pk_$i.log 2>&1
+  timeout 400 rocprofv3 --pmc $grp --kernel-trace --output-format csv -d /tmp/pk_$i -o p -- python "$ROOT/bench.py" --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-past-l3 > /tmp/pk_$i.log 2>&1
   python - /tmp/pk_$i "$K" <<'PY'
 import csv, sys, glob, collections
 d, k = sys.argv[1], sys.argv[2]

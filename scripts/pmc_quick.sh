@@ -5,7 +5,7 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pq_$c
-  timeout 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pq_$c -o p -- python "$ROOT/bench.py" --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-past-l3 --no-other-configs --sustained-seconds 0 > /dev/null 2>&1
+  timeout 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pq_$c -o p -- python "$ROOT/bench.py" --full --workload $W --steps 3 --warmup 1 --no-cpu-baseline --no-past-l3 --no-other-configs --sustained-seconds 0 > /dev/null 2>&1
 done
 python - <<'PY'
 import csv, collections, glob

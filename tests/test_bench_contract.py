@@ -14,8 +14,8 @@ pytestmark = pytest.mark.gpu
 
 def _bench(extra_env, *args):
     env = dict(os.environ, **extra_env)
-    # (--no-other-configs: the C3 / C4 / batch / host-cycle legs of the default run take half a minute and are the driver's bench run, not this contract)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-other-configs", "--sustained-seconds", "0.3", *args],
+    # (--full for the roofline and the sustained loop; --no-other-configs: the C3 / C4 / batch / host-cycle legs take half a minute and are not this contract)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-other-configs", "--sustained-seconds", "0.3", *args],
                          capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
@@ -29,6 +29,36 @@ def test_bench_line_small_window():
         assert key in r, key
     assert r["n_gpus"] == 1 and r["steps"] == 2 and r["value"] > 0 and r["dtype"] == "f64"
     assert r["roofline"]["bound"] == "hbm" and 0 < r["roofline"]["frac"] < 1.5
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times its steps and prints the headline keys only; --dump-outputs writes what the last step computed,
+    and the same arguments give the same inputs, hence the same outputs, in a second run."""
+    def run(d):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--n-kf", "40", "--n-lm", "4000",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+    r = run(tmp_path / "a")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in r, key
+    assert r["steps"] == 3 and r["value"] > 0 and r["ms_per_step"] > 0 and r["higher_is_better"] is True
+    for key in ("roofline", "roofline_mfma", "kernels", "sustained", "other_configs", "cpu_baseline"):
+        assert key not in r, key
+    import numpy as np
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("parameters", "iteration_cost", "summary")}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert a["parameters"].size > 3 * 4000 and np.isfinite(a["parameters"]).all()
+    assert a["summary"].shape == (1, 9) and a["summary"][0, 1] == r["config"]["final_cost"]
+    assert a["iteration_cost"].size >= 1 and a["iteration_cost"][0] == a["summary"][0, 0]
+    run(tmp_path / "b")
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in a}
+    assert all(b[n].shape == a[n].shape for n in a)
+    # (the costs repeat to 1e-9 as in test_bench_rccl_path_world_size_one; the solved values to the rounding of unordered sums)
+    assert np.allclose(b["summary"], a["summary"], rtol=1e-9, atol=0) and np.allclose(b["iteration_cost"], a["iteration_cost"], rtol=1e-9, atol=0)
+    assert np.abs(b["parameters"] - a["parameters"]).max() <= 1e-6 * max(1.0, np.abs(a["parameters"]).max())
 
 
 def test_bench_rccl_path_world_size_one():
