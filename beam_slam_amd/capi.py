@@ -112,6 +112,7 @@ SYMBOLS = [
     "evaluate", "num_residuals", "num_parameters_tangent", "tangent_offset", "covariance", "marginalize", "get_marginal",
     "reprojection_errors", "preintegrate", "triangulate", "time_reproj_jacobian_ms", "reproj_jacobian_bytes", "dense_solve", "plan_info",
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
+    "covariance_requests",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -304,6 +305,28 @@ class Solver:
         fn.argtypes = [C.c_void_p, C.c_int32, _ip, _dp]
         self._chk(fn(self._ctx, int(bl.size), bl.ctypes.data_as(_ip), out.ctypes.data_as(_dp)))
         return out
+
+    def covariance_requests(self, pairs):
+        """Graph::getCovariance(requests, matrices) (bsgpu_covariance_requests): the ts(a) x ts(b) marginal covariance of every
+        (block_a, block_b) pair, any non-constant block (landmarks included), from one linearisation.  Returns a list of arrays."""
+        pr = np.ascontiguousarray(np.asarray(pairs, np.int32).reshape(-1, 2))
+        n = pr.shape[0]
+        fn = self._f("covariance_requests")
+        fn.argtypes = [C.c_void_p, C.c_int32, _ip, C.POINTER(C.c_int64), _dp]
+        if n == 0:
+            self._chk(fn(self._ctx, 0, None, None, None))
+            return []
+        # sizes only (no device work): the tangent size of each distinct block from its (b, b) entry, then the offsets of the pairs
+        blocks = np.unique(pr)
+        diag = np.ascontiguousarray(np.repeat(blocks, 2).astype(np.int32))
+        off_d = np.zeros(blocks.size + 1, np.int64)
+        self._chk(fn(self._ctx, blocks.size, diag.ctypes.data_as(_ip), off_d.ctypes.data_as(C.POINTER(C.c_int64)), None))
+        ts = {int(b): int(round(np.sqrt(off_d[i + 1] - off_d[i]))) for i, b in enumerate(blocks)}
+        off = np.zeros(n + 1, np.int64)
+        self._chk(fn(self._ctx, n, pr.ctypes.data_as(_ip), off.ctypes.data_as(C.POINTER(C.c_int64)), None))
+        out = np.zeros(int(off[-1]))
+        self._chk(fn(self._ctx, n, pr.ctypes.data_as(_ip), None, out.ctypes.data_as(_dp)))
+        return [out[off[i]:off[i + 1]].reshape(ts[int(a)], ts[int(b)]) for i, (a, b) in enumerate(pr)]
 
     def marginalize(self, blocks, sizes):
         """fuse_constraints::marginalizeVariables at the current values: returns (kept_blocks, A, b, xbar), the payload

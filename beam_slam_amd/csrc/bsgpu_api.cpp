@@ -809,6 +809,118 @@ int bsgpu_covariance_joint(bsgpu_ctx* c, int32_t n_blocks, const int32_t* blocks
   return covariance_of(c, std::vector<int>(blocks, blocks + n_blocks), out);
 } catch (...) { return api_exception(c); }
 
+// Graph::getCovariance(requests, matrices) for any non-constant block, from one evaluation (k_cov.hip has the algebra).  Every distinct
+// block of the requests owns tangent-size rows: unit vectors for a pose-side block, the border rows V_l^-1 W_l of an eliminated landmark.
+// The rows ride through the factorisation 64 at a time (a block's rows stay in one pass); after each pass the forward-substituted rows
+// are copied into Y, and one launch forms every requested block from Y.  The system is assembled again for every pass after the first
+// (the factorisation overwrites it; the evaluation stays).
+constexpr size_t kCovRowsBudget = (size_t)1 << 30;   // bytes of kept rows (Y) one call may hold on the device
+int bsgpu_covariance_requests(bsgpu_ctx* c, int32_t n_req, const int32_t* pairs, int64_t* offsets, double* out) try {
+  if (!c) return BSGPU_ERR_INVALID;
+  if (n_req < 0 || (n_req > 0 && !pairs)) return fail(c, BSGPU_ERR_INVALID, "covariance_requests: bad argument");
+  if (n_req == 0) { if (offsets) offsets[0] = 0; return BSGPU_OK; }
+  int rc = finalize(c);
+  if (rc != BSGPU_OK) return rc;
+  for (int i = 0; i < 2 * n_req; ++i) {
+    const int b = pairs[i];
+    if (b < 0 || b >= c->nb) return fail(c, BSGPU_ERR_INVALID, "covariance_requests: block out of range");
+    if (c->toff[b] < 0) return fail(c, BSGPU_ERR_INVALID, "covariance_requests: constant block");
+  }
+  std::vector<int64_t> off(n_req + 1, 0);
+  for (int i = 0; i < n_req; ++i) off[i + 1] = off[i] + (int64_t)c->tsize[pairs[2 * i]] * c->tsize[pairs[2 * i + 1]];
+  if (offsets) std::memcpy(offsets, off.data(), sizeof(int64_t) * off.size());
+  if (!out) return BSGPU_OK;
+  if (!c->dense_ok) return fail(c, BSGPU_ERR_UNSUPPORTED, "covariance_requests: reduced system above the dense limit (block-sparse PCG path has no factor)");
+  // rows of the distinct blocks, packed into passes of <= 64
+  const int n_pose = c->n_pose;
+  auto kind_of = [&](int b) { return c->toff[b] < n_pose ? kCovUnit : (c->is_lm[b] == 2 ? kCovIdp : kCovLandmark); };
+  auto lm_of = [&](int b) { return kind_of(b) == kCovIdp ? c->toff[b] - c->idp.to0 : (c->toff[b] - n_pose) / 3; };
+  std::map<int, int> row_of;                  // block -> its first row in Y
+  std::vector<CovRow> rows;                   // the entries of all passes, pass by pass
+  std::vector<int> pass_entry{0}, pass_row{0};   // per pass: first entry, first row in Y (one more at the end)
+  int n_rows = 0, in_pass = 0;
+  for (int i = 0; i < 2 * n_req; ++i) {
+    const int b = pairs[i];
+    if (row_of.count(b)) continue;
+    const int ts = c->tsize[b];
+    if (in_pass + ts > 64) { pass_entry.push_back((int)rows.size()); pass_row.push_back(n_rows); in_pass = 0; }
+    row_of[b] = n_rows;
+    const int k = kind_of(b);
+    if (k == kCovUnit) for (int r = 0; r < ts; ++r) rows.push_back(CovRow{kCovUnit, c->plan.spos(c->toff[b] + r), in_pass + r, 0});
+    else rows.push_back(CovRow{k, lm_of(b), in_pass, 0});
+    n_rows += ts; in_pass += ts;
+  }
+  pass_entry.push_back((int)rows.size()); pass_row.push_back(n_rows);
+  const int n_pass = (int)pass_entry.size() - 1;
+  const int ldy = c->npad, n_cols = c->plan.T * 64;
+  if ((size_t)n_rows * ldy * sizeof(double) > kCovRowsBudget)
+    return fail(c, BSGPU_ERR_UNSUPPORTED, "covariance_requests: the kept rows (" + std::to_string(n_rows) + " x " + std::to_string(ldy) +
+                " doubles) exceed the 1 GiB device-memory budget of one call; split the requests");
+  std::vector<CovReq> req(n_req);
+  for (int i = 0; i < n_req; ++i) {
+    const int a = pairs[2 * i], b = pairs[2 * i + 1];
+    const int ka = kind_of(a), kb = kind_of(b);
+    CovReq& q = req[i];
+    q.ra = row_of[a]; q.ta = c->tsize[a]; q.rb = row_of[b]; q.tb = c->tsize[b];
+    q.sign = ((ka != kCovUnit) != (kb != kCovUnit)) ? -1 : 1;
+    q.lm_kind = (a == b && ka != kCovUnit) ? ka : kCovUnit;
+    q.lm_index = q.lm_kind != kCovUnit ? lm_of(a) : 0;
+    q.pad = 0;
+    q.out = off[i];
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  // one device buffer: Y | the output | the requests | the row entries
+  const size_t y_bytes = (size_t)n_rows * ldy * sizeof(double), o_bytes = ((size_t)off[n_req] * sizeof(double) + 255) & ~(size_t)255;
+  const size_t q_bytes = (sizeof(CovReq) * req.size() + 255) & ~(size_t)255, r_bytes = sizeof(CovRow) * rows.size();
+  unsigned char* buf = nullptr;
+  if (hipMalloc((void**)&buf, y_bytes + o_bytes + q_bytes + r_bytes) != hipSuccess) { (void)hipGetLastError(); return fail(c, BSGPU_ERR_DEVICE, "covariance_requests: out of device memory"); }
+  struct Free { unsigned char* p; ~Free() { (void)hipFree(p); } } free_buf{buf};
+  double* d_Y = reinterpret_cast<double*>(buf);
+  double* d_out = reinterpret_cast<double*>(buf + y_bytes);
+  CovReq* d_req = reinterpret_cast<CovReq*>(buf + y_bytes + o_bytes);
+  CovRow* d_rows = reinterpret_cast<CovRow*>(buf + y_bytes + o_bytes + q_bytes);
+  HIPCHK(c, hipMemcpyAsync(d_req, req.data(), sizeof(CovReq) * req.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(d_rows, rows.data(), r_bytes, hipMemcpyHostToDevice, s));
+  bsgpu_options o;
+  bsgpu_options_default(&o);
+  const bool was_pcg = c->use_pcg;
+  c->use_pcg = false;
+  *c->h_radius = 1e300;   // Lambda / radius -> 0: undamped normal equations
+  (void)hipMemcpyAsync(c->d_scal + SC_RADIUS, c->h_radius, sizeof(double), hipMemcpyHostToDevice, s);
+  eval_all(c, c->d_x, true, SC_COST_X);
+  c->spec_J = false;
+  bool singular = false;
+  for (int p = 0; p < n_pass && rc == BSGPU_OK && !singular; ++p) {
+    const int n_ent = pass_entry[p + 1] - pass_entry[p], r0 = pass_row[p], nr = pass_row[p + 1] - r0;
+    assemble(c, o, 1e300, true, true);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      launch_cov_rows(s, c->d_S, c->npad, c->plan.rhs_row, d_rows + pass_entry[p], n_ent, c->d_dpos, c->vis, c->idp);
+      DenseDev D0{c->d_nreal, c->d_rows_flat, c->d_panels, c->d_Lp, c->d_Vinv,
+                  c->d_bs_desc, c->d_chain_begin, c->d_chain_end, c->d_tile_sync, c->d_ftasks, c->d_fsync};
+      D0.Winv = c->d_Winv; D0.tile_tot = c->d_tile_tot; D0.rhs_rows = nr;
+      D0.ftasks_plain = c->d_ftasks_plain; D0.tile_tot_plain = c->d_tile_tot_plain; D0.n_ftasks_plain = c->n_ftasks_plain;
+      dense_factor(s, c->plan, D0, c->d_S, c->d_scal);
+      (void)hipMemcpyAsync(d_Y + (size_t)r0 * ldy, c->d_Lp + (size_t)c->plan.rhs_row * ldy, sizeof(double) * nr * ldy, hipMemcpyDeviceToDevice, s);
+      rc = fetch_scalars(c);
+      if (rc != BSGPU_OK || !(c->h_scal[SC_CHOL_FAIL] == 2.0 && c->d_ftasks)) break;
+      // a wait inside the single-launch factorisation timed out (a shared device): as covariance_of, the launch-per-step path from here on
+      c->d_ftasks = nullptr;
+      assemble(c, o, 1e300, true, true);
+    }
+    if (rc == BSGPU_OK && c->h_scal[SC_CHOL_FAIL] > 0.0) singular = true;
+  }
+  c->use_pcg = was_pcg;
+  if (rc != BSGPU_OK) return rc;
+  if (singular) return fail(c, BSGPU_ERR_NUMERIC, "covariance_requests: J^T J is singular at the current values (gauge freedom or unobserved block)");
+  launch_cov_gram(s, d_req, n_req, d_Y, ldy, n_cols, c->vis.Linv, c->idp.linv, d_out);
+  HIPCHK(c, hipMemcpyAsync(out, d_out, sizeof(double) * off[n_req], hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipStreamSynchronize(s));
+  for (int64_t i = 0; i < off[n_req]; ++i)
+    if (!std::isfinite(out[i])) return fail(c, BSGPU_ERR_NUMERIC, "covariance_requests: J^T J is singular at the current values (gauge freedom or unobserved block)");
+  return BSGPU_OK;
+} catch (...) { return api_exception(c); }
+
 // The payload of the index-th dense linear prior, replaced in place: the finalized device structure stays (same blocks, rows, columns).
 int bsgpu_update_marginal(bsgpu_ctx* c, int32_t index, int32_t n_rows, int32_t n_cols, int32_t n_xbar, const double* A, const double* b,
                           const double* xbar) try {

@@ -476,6 +476,26 @@ void launch_marg_schur(hipStream_t s, const double* S, int ld, int rhs_row, cons
                        double* M, double* g, double* diag0, int* pivot_ok, double* status, double* A, double* b);
 void launch_cov_units(hipStream_t s, double* S, int ld, int rhs_row, const int* cols_dev, int n);
 void launch_cov_dots(hipStream_t s, const double* Lp, int ld, int rhs_row, int n_cols, int ta, int row_b0, int tb, double* out);
+// batched covariance requests (k_cov.hip, bsgpu_covariance_requests): the rows one requested block puts into the rhs tile ...
+enum CovRowKind { kCovUnit = 0, kCovLandmark = 1, kCovIdp = 2 };
+struct CovRow {
+  int kind;    // CovRowKind
+  int index;   // kCovUnit: solver position of the unit entry; kCovLandmark / kCovIdp: the eliminated landmark (Visual / IdpElim numbering)
+  int row;     // first row of the rhs tile it writes (kCovLandmark: 3 rows, the others 1)
+  int pad;
+};
+// ... and one requested ta x tb block: sign * (rows ra.. . rows rb..) + [landmark_a == landmark_b] V_l^-1
+struct CovReq {
+  int ra, ta, rb, tb;
+  int sign;       // -1 when exactly one of the two blocks is an eliminated landmark
+  int lm_kind;    // kCovLandmark / kCovIdp: a == b, an eliminated landmark whose V_l^-1 is added; else kCovUnit
+  int lm_index;
+  int pad;
+  int64_t out;    // offset of the block in the output
+};
+void launch_cov_rows(hipStream_t s, double* S, int ld, int rhs_row, const CovRow* rows, int n_rows, const int* dpos, const Visual& v, const IdpElim& e);
+void launch_cov_gram(hipStream_t s, const CovReq* req, int n_req, const double* Y, int ldy, int n_cols, const double* lm_linv, const double* idp_linv,
+                     double* out);
 void launch_marg_eval(hipStream_t s, const MargDev& m, const double* x, bool with_J, double* cost_part /* rows */);
 void launch_marg_assemble(hipStream_t s, const MargDev& m, double* S, int ld, int rhs_row, double* grad, double* hdiag, const int* perm);
 void launch_marg_mcc(hipStream_t s, const MargDev& m, const double* delta_tan, double* part /* rows */);

@@ -17,6 +17,11 @@
 
 #include "bs_constraints.h"
 
+// the batched covariance entry point is optional in a back-end (a library built before it has only bsgpu_covariance):
+// getCovariance() takes it when it resolves, and the per-pair loop otherwise
+extern "C" int bsgpu_covariance_requests(bsgpu_ctx* ctx, int32_t n_requests, const int32_t* block_pairs, int64_t* offsets, double* out)
+    __attribute__((weak));
+
 namespace ceres_compat {  // the ceres::Solver fields the reference sets (vio.yaml:7-17) and reads (fixed_lag_smoother.cpp:286,705-716)
 enum TerminationType { CONVERGENCE = 0, NO_CONVERGENCE = 1, FAILURE = 2 };
 struct SolverOptions {
@@ -661,20 +666,37 @@ class GpuGraph {
 
   // fuse_core::Graph::getCovariance(covariance_requests, covariance_matrices) in tangent space (the form
   // bs_publishers/src/odometry_3d_publisher.cpp:82 consumes): one row-major localSize(a) x localSize(b) matrix per
-  // requested pair, marginal covariance at the variables' current values.  Pose-side variables only: landmarks are
-  // eliminated by the solver (throws, like fuse does for an uncomputable request).
+  // requested pair, marginal covariance at the variables' current values.  Any variable that is not held constant, landmarks
+  // included: every pair from one linearisation (bsgpu_covariance_requests).  A back-end without that entry point answers
+  // pair by pair through bsgpu_covariance (pose-side variables only).
   void getCovariance(const std::vector<std::pair<fuse_core::UUID, fuse_core::UUID>>& covariance_requests,
                      std::vector<std::vector<double>>& covariance_matrices) {
     Flat& f = flat_;
     covariance_matrices.clear();
     if (covariance_requests.empty()) return;
     if (!flatten(f)) throw std::runtime_error("getCovariance: empty graph");
+    std::vector<int32_t> pairs;
+    std::vector<size_t> sizes;
     for (const auto& rq : covariance_requests) {
       if (!variableExists(rq.first) || !variableExists(rq.second)) throw std::out_of_range("getCovariance: variable not in graph");
-      const int32_t a = blockIndexOf(f, rq.first), b = blockIndexOf(f, rq.second);
-      const size_t ta = getVariable(rq.first).localSize(), tb = getVariable(rq.second).localSize();
-      std::vector<double> m(ta * tb);
-      check(bsgpu_covariance(ctx(), a, b, m.data()));
+      pairs.push_back(blockIndexOf(f, rq.first)); pairs.push_back(blockIndexOf(f, rq.second));
+      sizes.push_back(getVariable(rq.first).localSize()); sizes.push_back(getVariable(rq.second).localSize());
+    }
+    const size_t n = covariance_requests.size();
+    if (bsgpu_covariance_requests) {
+      std::vector<int64_t> offsets(n + 1);
+      check(bsgpu_covariance_requests(ctx(), (int32_t)n, pairs.data(), offsets.data(), nullptr));
+      std::vector<double> all((size_t)offsets[n]);
+      check(bsgpu_covariance_requests(ctx(), (int32_t)n, pairs.data(), nullptr, all.data()));
+      for (size_t i = 0; i < n; ++i) {
+        if ((size_t)(offsets[i + 1] - offsets[i]) != sizes[2 * i] * sizes[2 * i + 1]) throw std::logic_error("getCovariance: tangent sizes disagree");
+        covariance_matrices.emplace_back(all.begin() + offsets[i], all.begin() + offsets[i + 1]);
+      }
+      return;
+    }
+    for (size_t i = 0; i < n; ++i) {
+      std::vector<double> m(sizes[2 * i] * sizes[2 * i + 1]);
+      check(bsgpu_covariance(ctx(), pairs[2 * i], pairs[2 * i + 1], m.data()));
       covariance_matrices.push_back(std::move(m));
     }
   }

@@ -137,7 +137,7 @@ enum {
    *           landmark in the anchor camera, InverseDepthLandmark::bearing())
    *   An inverse-depth scalar that only such factors use is eliminated on the
    *   landmark side like a Euclidean landmark (csrc/k_idp.hip; its covariance
-   *   cannot be queried then; BSGPU_IDP_ELIM=0 at finalize keeps it in the
+   *   is then answered by bsgpu_covariance_requests only; BSGPU_IDP_ELIM=0 at finalize keeps it in the
    *   reduced system).  use_idp is off in every shipped configuration.         */
   BSGPU_F_IDP_REPROJ = 10,
   /* bs_constraints::InverseDepthReprojectionConstraintUnary
@@ -419,6 +419,16 @@ int bsgpu_covariance(bsgpu_ctx* ctx, int32_t block_a, int32_t block_b, double* o
  * bsgpu_covariance.  What a submap's summary of itself on its boundary key frames is made of (the unit of independence of
  * bs_models/src/lib/global_mapping/submap_refinement.cpp:35-115; shared-pose consensus, beam_slam_amd/sharding.py).            */
 int bsgpu_covariance_joint(bsgpu_ctx* ctx, int32_t n_blocks, const int32_t* blocks, double* out);
+/* Graph::getCovariance(requests, matrices): the marginal covariance blocks of n_requests (block_a, block_b) pairs, in tangent space,
+ * at the current values, from ONE undamped linearisation.  Any non-constant block: pose-side blocks, Euclidean landmarks (eliminated or
+ * not), inverse-depth scalars.  block_pairs[2 * n_requests]; offsets[n_requests + 1] (may be NULL) receives where each ts(a) x ts(b)
+ * row-major matrix starts in out; out == NULL: sizes only.  n_requests == 0 is accepted (offsets[0] = 0).
+ * Every requested block contributes tangent-size rows (a pose-side block its unit vectors, an eliminated landmark the rows of
+ * V_l^-1 W_l); they ride through the factorisation 64 at a time, so k rows take ceil(k / 64) factorisations (blocks are not split
+ * between passes).  The factored rows are kept on the device: (rows) x (reduced dimension, padded) doubles, at most 1 GiB.
+ * Errors: a bad block index, a constant block, a NULL pair list -> INVALID; a reduced system above the dense limit or kept rows above
+ * the budget -> UNSUPPORTED; a singular J^T J -> NUMERIC.                                                                          */
+int bsgpu_covariance_requests(bsgpu_ctx* ctx, int32_t n_requests, const int32_t* block_pairs, int64_t* offsets, double* out);
 
 /* ---- factor producers either side of the solve ---------
  * Pixel error |z - projection| of every reprojection factor (types REPROJ then REPROJ_ONLINE_CALIB, insertion
