@@ -112,7 +112,7 @@ SYMBOLS = [
     "evaluate", "num_residuals", "num_parameters_tangent", "tangent_offset", "covariance", "marginalize", "get_marginal",
     "reprojection_errors", "preintegrate", "triangulate", "time_reproj_jacobian_ms", "reproj_jacobian_bytes", "dense_solve", "plan_info",
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
-    "covariance_requests",
+    "covariance_requests", "localize_frames",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -327,6 +327,31 @@ class Solver:
         out = np.zeros(int(off[-1]))
         self._chk(fn(self._ctx, n, pr.ctypes.data_as(_ip), None, out.ctypes.data_as(_dp)))
         return [out[off[i]:off[i + 1]].reshape(ts[int(a)], ts[int(b)]) for i, (a, b) in enumerate(pr)]
+
+    def localize_frames(self, obs_start, pixels, q_init, p_init, camera, points=None, lm_block=None, loss_kind=LOSS_TRIVIAL, loss_a=1.0,
+                        sqrt_info=1.0, truncate_pixels=False, min_points=20, image_width=0, image_height=0, options=None):
+        """VisualOdometry::LocalizeFrame for a batch of frames (bsgpu_localize_frames): frame f holds observations
+        [obs_start[f], obs_start[f+1]) with pixels (n x 2) and either world points (n x 3) or landmark blocks (n) of this context.
+        Returns a dict of arrays: q (F x 4), p (F x 3), cov (F x 6 x 6, [p, q tangent]), avg_reproj, final_cost, iterations, status."""
+        os_ = np.ascontiguousarray(obs_start, np.int32)
+        F = os_.size - 1
+        pix = np.ascontiguousarray(pixels, np.float64).reshape(-1, 2)
+        pts = None if points is None else np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        lmb = None if lm_block is None else np.ascontiguousarray(lm_block, np.int32)
+        cam = np.ascontiguousarray(np.broadcast_to(np.asarray(camera, np.int32), (F,)))
+        qi = np.ascontiguousarray(q_init, np.float64).reshape(F, 4)
+        pi = np.ascontiguousarray(p_init, np.float64).reshape(F, 3)
+        o = options if options is not None else self.options_default()
+        out = dict(q=np.zeros((F, 4)), p=np.zeros((F, 3)), cov=np.zeros((F, 6, 6)), avg_reproj=np.zeros(F), final_cost=np.zeros(F),
+                   iterations=np.zeros(F, np.int32), status=np.zeros(F, np.int32))
+        fn = self._f("localize_frames")
+        fn.argtypes = [C.c_void_p, C.c_int32, _ip, _dp, _dp, _ip, _ip, _dp, _dp, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32,
+                       C.c_int32, C.c_int32, C.POINTER(Options), _dp, _dp, _dp, _dp, _dp, _ip, _ip]
+        self._chk(fn(self._ctx, F, _ptr(os_, _ip), _ptr(pix, _dp), _ptr(pts, _dp), _ptr(lmb, _ip), _ptr(cam, _ip), _ptr(qi, _dp), _ptr(pi, _dp),
+                     int(loss_kind), float(loss_a), float(sqrt_info), 1 if truncate_pixels else 0, int(min_points), int(image_width),
+                     int(image_height), C.byref(o), _ptr(out["q"], _dp), _ptr(out["p"], _dp), _ptr(out["cov"], _dp),
+                     _ptr(out["avg_reproj"], _dp), _ptr(out["final_cost"], _dp), _ptr(out["iterations"], _ip), _ptr(out["status"], _ip)))
+        return out
 
     def marginalize(self, blocks, sizes):
         """fuse_constraints::marginalizeVariables at the current values: returns (kept_blocks, A, b, xbar), the payload

@@ -1058,6 +1058,96 @@ int bsgpu_triangulate(bsgpu_ctx* c, int32_t n_tracks, const int32_t* track_start
   return BSGPU_OK;
 } catch (...) { return api_exception(c); }
 
+int bsgpu_localize_frames(bsgpu_ctx* c, int32_t n_frames, const int32_t* obs_start, const double* pixels, const double* points,
+                          const int32_t* lm_block, const int32_t* camera, const double* q_init, const double* p_init,
+                          int32_t loss_kind, double loss_a, double sqrt_info, int32_t truncate_pixels, int32_t min_points,
+                          int32_t image_width, int32_t image_height, const bsgpu_options* options, double* q_out, double* p_out,
+                          double* cov_out, double* avg_reproj, double* final_cost, int32_t* iterations, int32_t* status) try {
+  if (!c) return BSGPU_ERR_INVALID;
+  if (n_frames < 0 || !obs_start || !camera || !q_init || !p_init || !options || !q_out || !p_out || !status)
+    return fail(c, BSGPU_ERR_INVALID, "localize_frames: null argument");
+  if ((points == nullptr) == (lm_block == nullptr)) return fail(c, BSGPU_ERR_INVALID, "localize_frames: pass exactly one of points and lm_block");
+  if (loss_kind < BSGPU_LOSS_TRIVIAL || loss_kind > BSGPU_LOSS_HUBER) return fail(c, BSGPU_ERR_INVALID, "unknown loss kind");
+  if (obs_start[0] != 0) return fail(c, BSGPU_ERR_INVALID, "localize_frames: obs_start[0] must be 0");
+  for (int f = 0; f < n_frames; ++f) {
+    if (obs_start[f + 1] < obs_start[f]) return fail(c, BSGPU_ERR_INVALID, "localize_frames: obs_start must be non-decreasing");
+    if (camera[f] < 0 || camera[f] >= (int)c->cams.size()) return fail(c, BSGPU_ERR_INVALID, "camera index out of range");
+  }
+  const int n_obs = obs_start[n_frames];
+  if (n_obs > 0 && !pixels) return fail(c, BSGPU_ERR_INVALID, "localize_frames: null pixels");
+  std::vector<int32_t> pt_off;
+  if (lm_block) {
+    if (!c->finalized || !c->d_x) return fail(c, BSGPU_ERR_INVALID, "localize_frames: lm_block needs the context's values on the device (finalize or solve first)");
+    pt_off.resize((size_t)n_obs);
+    for (int o = 0; o < n_obs; ++o) {
+      const int b = lm_block[o];
+      if (b < 0 || b >= c->nb) return fail(c, BSGPU_ERR_INVALID, "localize_frames: block out of range");
+      if (c->size[b] != 3 || c->manifold[b] != BSGPU_MANIFOLD_EUCLIDEAN) return fail(c, BSGPU_ERR_INVALID, "localize_frames: lm_block must name 3-d Euclidean blocks");
+      pt_off[o] = c->off[b];
+    }
+  }
+  if (n_frames == 0) return BSGPU_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // one device buffer: inputs [obs_start | camera | pt_off | cameras | pixels | points | poses], outputs [per-frame doubles | ints]
+  std::vector<DevCamera> cams(c->cams.size());
+  for (size_t i = 0; i < cams.size(); ++i) {
+    const bsgpu_camera& hc = c->cams[i];
+    cams[i].fx = hc.fx; cams[i].fy = hc.fy; cams[i].cx = hc.cx; cams[i].cy = hc.cy;
+    std::memcpy(cams[i].R, hc.R_cam_baselink, sizeof(cams[i].R));
+    std::memcpy(cams[i].t, hc.t_cam_baselink, sizeof(cams[i].t));
+  }
+  std::vector<double> pose((size_t)7 * n_frames);
+  for (int f = 0; f < n_frames; ++f) {
+    std::memcpy(&pose[7 * (size_t)f], q_init + 4 * (size_t)f, 4 * sizeof(double));
+    std::memcpy(&pose[7 * (size_t)f + 4], p_init + 3 * (size_t)f, 3 * sizeof(double));
+  }
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_start = al(sizeof(int32_t) * ((size_t)n_frames + 1)), b_cam = al(sizeof(int32_t) * (size_t)n_frames),
+               b_off = al(sizeof(int32_t) * pt_off.size()), b_cams = al(sizeof(DevCamera) * cams.size()),
+               b_pix = al(sizeof(double) * 2 * (size_t)n_obs), b_pts = points ? al(sizeof(double) * 3 * (size_t)n_obs) : 0,
+               b_pose = al(sizeof(double) * pose.size());
+  const size_t in_bytes = b_start + b_cam + b_off + b_cams + b_pix + b_pts + b_pose;
+  const size_t out_d = sizeof(double) * kLocOutStride * (size_t)n_frames, out_i = sizeof(int32_t) * 2 * (size_t)n_frames;
+  std::vector<char> h_in(in_bytes);
+  std::vector<char> h_out(out_d + out_i);
+  size_t at = 0;
+  auto put = [&](const void* src, size_t bytes, size_t span) { if (bytes) std::memcpy(h_in.data() + at, src, bytes); const size_t o = at; at += span; return o; };
+  const size_t o_start = put(obs_start, sizeof(int32_t) * ((size_t)n_frames + 1), b_start);
+  const size_t o_cam = put(camera, sizeof(int32_t) * (size_t)n_frames, b_cam);
+  const size_t o_off = put(pt_off.data(), sizeof(int32_t) * pt_off.size(), b_off);
+  const size_t o_cams = put(cams.data(), sizeof(DevCamera) * cams.size(), b_cams);
+  const size_t o_pix = put(pixels, sizeof(double) * 2 * (size_t)n_obs, b_pix);
+  const size_t o_pts = put(points, points ? sizeof(double) * 3 * (size_t)n_obs : 0, b_pts);
+  const size_t o_pose = put(pose.data(), sizeof(double) * pose.size(), b_pose);
+  char* d = nullptr;
+  if (hipMalloc((void**)&d, in_bytes + out_d + out_i) != hipSuccess) { (void)hipGetLastError(); return fail(c, BSGPU_ERR_DEVICE, "localize_frames: out of device memory"); }
+  hipError_t e = hipMemcpyAsync(d, h_in.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    launch_localize(c->stream, n_frames, (const int*)(d + o_start), (const double2*)(d + o_pix), points ? (const double*)(d + o_pts) : nullptr,
+                    lm_block ? (const int*)(d + o_off) : nullptr, lm_block ? c->d_x : nullptr, (const DevCamera*)(d + o_cams),
+                    (const int*)(d + o_cam), (const double*)(d + o_pose), loss_kind, loss_a, sqrt_info, truncate_pixels != 0 ? 1 : 0,
+                    min_points, image_width, image_height, *options, (double*)(d + in_bytes), (int*)(d + in_bytes + out_d));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d + in_bytes, out_d + out_i, hipMemcpyDeviceToHost, c->stream);
+  const hipError_t e2 = hipStreamSynchronize(c->stream);
+  (void)hipFree(d);
+  if (e != hipSuccess || e2 != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "localize_frames: device error");
+  const double* od = (const double*)h_out.data();
+  const int32_t* oi = (const int32_t*)(h_out.data() + out_d);
+  for (int f = 0; f < n_frames; ++f) {
+    const double* r = od + (size_t)kLocOutStride * f;
+    std::memcpy(q_out + 4 * (size_t)f, r, 4 * sizeof(double));
+    std::memcpy(p_out + 3 * (size_t)f, r + 4, 3 * sizeof(double));
+    if (final_cost) final_cost[f] = r[7];
+    if (avg_reproj) avg_reproj[f] = r[8];
+    if (cov_out) std::memcpy(cov_out + 36 * (size_t)f, r + 9, 36 * sizeof(double));
+    if (iterations) iterations[f] = oi[2 * f];
+    status[f] = oi[2 * f + 1];
+  }
+  return BSGPU_OK;
+} catch (...) { return api_exception(c); }
+
 double bsgpu_time_reproj_jacobian_ms(bsgpu_ctx* c, int32_t reps) {
   if (!c) return -1.0;
   if (finalize(c) != BSGPU_OK || c->vis.n == 0 || reps <= 0) return -1.0;

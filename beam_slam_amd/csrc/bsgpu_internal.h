@@ -10,6 +10,8 @@
 
 #include "dense_plan.h"
 
+struct bsgpu_options;   // include/bsgpu.h
+
 namespace bsg {
 
 // ---- device-side tables -------------------------------------------------------------------------
@@ -505,6 +507,14 @@ void launch_preintegrate(hipStream_t s, int n_int, const int* sample_start, cons
                          const double* t_end, const double* bg, const double* ba, const double* covs, double info_weight, double* out);
 void launch_triangulate(hipStream_t s, int n_tracks, const int* track_start, const int2* pose_off, const double2* pix, const double* x,
                         const DevCamera& cam, bool truncate, double max_dist, double max_reproj, double* points, int* status);
+// frame localisation (k_loc.hip, bsgpu_localize_frames): one workgroup per frame; pts (3 per observation) or pt_off (offset of the
+// observation's landmark block in x); pose_in 7 per frame (q wxyz, p); out kLocOutStride doubles per frame [q | p | cost | average
+// reprojection | covariance 6x6 of (p, theta)], out_i 2 per frame [iterations, status]
+constexpr int kLocOutStride = 45;
+void launch_localize(hipStream_t s, int n_frames, const int* obs_start, const double2* pix, const double* pts, const int* pt_off,
+                     const double* x, const DevCamera* cams, const int* cam_of, const double* pose_in, int loss_kind, double loss_a,
+                     double sqrt_info, int truncate, int min_points, int width, int height, const bsgpu_options& opt, double* out,
+                     int* out_i);
 // device-side flattening of the reprojection factors (k_flatten.hip): 0 = done, 1 = take the host path, < 0 = device error.
 // `res` non-null: the raw table is already on the device, its block columns naming caller slots (SlotMirror, bsgpu_ctx.h)
 struct FlattenResident { const int* idx; const double* consts; const int* loss_kind; const double* loss_a; const int* slot_map; };

@@ -463,6 +463,38 @@ int bsgpu_triangulate(bsgpu_ctx* ctx, int32_t n_tracks, const int32_t* track_sta
                       const int32_t* p_block, const double* pixels, int32_t camera, int32_t truncate_pixels,
                       double max_dist, double max_reproj, double* points, int32_t* status);
 
+/* Frame localisation for a batch of frames — VisualOdometry::LocalizeFrame (bs_models/src/visual_odometry.cpp:217-300): the
+ * frame's 2D-3D pairs (GetPixelPointPairs, :612-650), the required_points_to_refine gate, the robust refinement of the pose with
+ * its 6x6 covariance ([EXT] beam_cv::PoseRefinement::RefinePose, :240-248) and the screening average of ComputeAverageReprojection
+ * (:1247-1272).  libbeam's PoseRefinement is not in the reference checkout, so what PoseRefinement(0.02, true, 0.2) (:72) sets
+ * cannot be read: the loss and the LM options are arguments.  The optimisation itself is, by construction, the one-pose
+ * BSGPU_F_REPROJ problem: minimise 1/2 sum rho(|w (z - pi(K, T_cam_baselink T_WORLD_BASELINK^-1 P))|^2) over the baselink pose
+ * (orientation on BSGPU_MANIFOLD_QUAT_RIGHT, position Euclidean) with bsgpu_solve's trust-region loop (Ceres LM, Jacobi scaling,
+ * tolerance exits, invalid-step counting); max_solver_time_in_seconds is not honoured and the linear-solver fields are ignored.
+ *   frame f holds observations [obs_start[f], obs_start[f+1]) (obs_start[0] == 0, non-decreasing); pixels: 2 per observation
+ *   (truncated to integers when truncate_pixels != 0, the reference's cast<int>(), for the solve and for the average alike).
+ *   points: 3 per observation, world frame; OR lm_block: per observation a 3-d Euclidean block of ctx, read at its CURRENT device
+ *   values (the context must have been finalized or solved).  Exactly one of the two.
+ *   camera: per frame, an index into the bsgpu_set_cameras table.  q_init / p_init: per frame T_WORLD_BASELINK (wxyz, xyz).
+ *   loss_kind / loss_a: BSGPU_LOSS_* and its scale; sqrt_info: w of every pair.  min_points: required_points_to_refine.
+ *   image_width / image_height: bounds of the average (<= 0: no bounds check).
+ * Outputs per frame: q_out / p_out; cov_out (36, may be NULL): the marginal covariance (J^T J)^-1 of [p (3), q tangent (3)] at the
+ * returned pose from the undamped, loss-corrected J^T J — bsgpu_covariance_joint({p, q}) of the same problem, in the (x, y, z, roll,
+ * pitch, yaw) order LocalizeFrame converts to.  libbeam expresses its covariance on T_CAMERA_WORLD's parameters; this one is on the
+ * baselink pose.  avg_reproj (may be NULL): sum of |z - pi| over the pairs with P_c.z > 0 inside the image, divided by ALL of the
+ * frame's pairs (0 for an empty frame).  final_cost, iterations (may be NULL).  status: 0 refined (converged or at the iteration
+ * cap), 1 fewer than min_points observations (pose returned unchanged, nothing solved), 2 unusable (non-finite values or the
+ * invalid-step limit), 3 refined but J^T J singular (a Cholesky pivot not positive or not finite): covariance NaN.  NaN also in
+ * cov_out for statuses 1 and 2.
+ * The context is not changed (values, iteration record, finalize state); points-only mode needs nothing but cameras.  A frame's
+ * results do not depend on the other frames of the call.  Argument errors (bad camera index, an lm_block that is not a 3-d Euclidean
+ * block, both or neither of points / lm_block, lm_block without device values, a malformed obs_start) -> INVALID.           */
+int bsgpu_localize_frames(bsgpu_ctx* ctx, int32_t n_frames, const int32_t* obs_start, const double* pixels, const double* points,
+                          const int32_t* lm_block, const int32_t* camera, const double* q_init, const double* p_init,
+                          int32_t loss_kind, double loss_a, double sqrt_info, int32_t truncate_pixels, int32_t min_points,
+                          int32_t image_width, int32_t image_height, const bsgpu_options* options, double* q_out, double* p_out,
+                          double* cov_out, double* avg_reproj, double* final_cost, int32_t* iterations, int32_t* status);
+
 /* ---- measurement helpers (used by bench.py only) --------------------------- */
 /* Launches the Jacobian-evaluation kernel of the reprojection factors `reps`
  * times on the context's stream between two HIP events and returns the average
