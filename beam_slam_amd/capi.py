@@ -26,7 +26,8 @@ F_REL_VEC3 = 8
 F_GRAVITY = 9
 F_IDP_REPROJ = 10
 F_IDP_REPROJ_UNARY = 11
-F_NUM_TYPES = 12
+F_UNICYCLE = 12
+F_NUM_TYPES = 13
 
 LINEAR_AUTO, LINEAR_SCHUR_CHOLESKY, LINEAR_PCG, LINEAR_SCHUR_PCG = 0, 1, 2, 3
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2

@@ -1190,7 +1190,7 @@ int64_t bsgpu_eval_bytes(const bsgpu_ctx* c) {
   // (idx, consts, residuals, tangent Jacobian columns) per type, in doubles / ints as the tables hold them
   static const struct { int idx, consts, res, jcols; } L[BSGPU_F_NUM_TYPES] = {
       {4, 3, 2, 9}, {6, 3, 2, 9}, {10, 287, 15, 30}, {5, 241, 15, 15}, {6, 43, 6, 12}, {4, 43, 6, 12}, {2, 43, 6, 6}, {1, 12, 3, 3},
-      {2, 12, 3, 6}, {1, 7, 2, 3}, {6, 6, 2, 13}, {4, 6, 2, 7}};
+      {2, 12, 3, 6}, {1, 7, 2, 3}, {6, 6, 2, 13}, {4, 6, 2, 7}, {10, 226, 15, 30}};
   int64_t b = (int64_t)c->vis.n * 200 + (int64_t)c->h_x.size() * 8;
   for (int t = 2; t < BSGPU_F_NUM_TYPES && t < kNumInternal; ++t)
     b += (int64_t)c->small[t].n * (4 * L[t].idx + 8 * (L[t].consts + L[t].res + L[t].res * L[t].jcols));

@@ -55,7 +55,7 @@ bool shape_of(const bsgpu_ctx* c, WinShape& w) {
     for (int t : {(int)BSGPU_F_RELPOSE_EXT, (int)BSGPU_F_RELPOSE}) if (w.rel_t < 0 && c->small[t].n > 0) w.rel_t = t;
   const bool imu_carried = w.imu_pair && (w.vis || w.rel_t >= 0);
   for (int t = 2; t < kNumInternal; ++t) {
-    if (!c->small[t].n || t == w.rel_t) continue;
+    if (!c->small[t].n || t == w.rel_t || t == BSGPU_F_UNICYCLE) continue;   // (the unicycle factors: a launch of their own, t_eval_uni)
     if (imu_carried && (t == BSGPU_F_IMU_DELTA || t == BSGPU_F_IMU_PRIOR)) continue;
     w.set_t[w.n_set++] = t;
   }
@@ -121,7 +121,7 @@ struct BatchPlan {
   BatchDyn* d_dyn = nullptr;
   std::vector<void*> dev_allocs;
   // [3]: at x (rejected / first steps) | cost only at the candidate | residuals + Jacobians at the candidate, ahead of the decision
-  BatchArgTable t_eval_vis[3], t_eval_rel[3], t_eval_set[3], t_eval_marg[3], t_marg_asm, t_marg_mcc, t_idp_lm, t_idp_view, t_idp_pairs, t_idp_backsub;
+  BatchArgTable t_eval_vis[3], t_eval_rel[3], t_eval_set[3], t_eval_marg[3], t_eval_uni[3], t_marg_asm, t_marg_mcc, t_idp_lm, t_idp_view, t_idp_pairs, t_idp_backsub;
   BatchArgTable t_lm, t_lm_tail, t_zero, t_pairs, t_pairs_band, t_asm_set, t_asm_seg, t_gn, t_chol, t_bs[4], t_backsub, t_small_mcc, t_reduce, t_accept, t_backup;
   std::vector<int> bs_form;
   size_t max_tasks = 0;
@@ -132,7 +132,9 @@ struct BatchPlan {
   std::vector<BatchArgTable*> tables() {
     std::vector<BatchArgTable*> v = {&t_lm, &t_lm_tail, &t_zero, &t_pairs, &t_pairs_band, &t_asm_set, &t_asm_seg, &t_gn, &t_chol, &t_bs[0], &t_bs[1], &t_bs[2], &t_bs[3],
                                      &t_backsub, &t_small_mcc, &t_reduce, &t_accept, &t_backup};
-    for (int i = 0; i < 3; ++i) { v.push_back(&t_eval_vis[i]); v.push_back(&t_eval_rel[i]); v.push_back(&t_eval_set[i]); v.push_back(&t_eval_marg[i]); }
+    for (int i = 0; i < 3; ++i) {
+      v.push_back(&t_eval_vis[i]); v.push_back(&t_eval_rel[i]); v.push_back(&t_eval_set[i]); v.push_back(&t_eval_marg[i]); v.push_back(&t_eval_uni[i]);
+    }
     v.push_back(&t_marg_asm); v.push_back(&t_marg_mcc); v.push_back(&t_idp_lm); v.push_back(&t_idp_view); v.push_back(&t_idp_pairs); v.push_back(&t_idp_backsub);
     return v;
   }
@@ -238,6 +240,8 @@ bool build_plan(BatchPlan& P, bsgpu_ctx* const* ctxs, int n, const bsgpu_options
       double* ps[kNumInternal];
       for (int i = 0; i < sh.n_set; ++i) { gs[i] = c->small[sh.set_t[i]]; ps[i] = part[sh.set_t[i]]; }
       if (!batchargs_small_eval_set(P.t_eval_set[v], gs, ps, sh.n_set, xs[v], c->d_losses)) return false;
+      // (no unicycle factors: n = 0 gives the entry a zero grid)
+      batchargs_unicycle_eval(P.t_eval_uni[v], c->small[BSGPU_F_UNICYCLE], xs[v], c->d_losses, part[BSGPU_F_UNICYCLE]);
       if (!batchargs_marg_eval(P.t_eval_marg[v], mg ? &mg->dev : nullptr, xs[v], mg ? (cand ? mg->part_cand : mg->part) : nullptr)) return false;
     }
     // ---- assembly (assemble())
@@ -349,6 +353,7 @@ void evals(BatchPlan& P, int v, const BatchDyn* dd, int list, int n, bool with_J
   launch_visual_imu_eval_batch(P.stream, P.t_eval_vis[v], dd, list, n, with_J);
   launch_relpose_imu_eval_batch(P.stream, P.t_eval_rel[v], dd, list, n, with_J);
   launch_small_eval_set_batch(P.stream, P.t_eval_set[v], dd, list, n, with_J);
+  launch_unicycle_eval_batch(P.stream, P.t_eval_uni[v], dd, list, n, with_J);
   launch_marg_eval_batch(P.stream, P.t_eval_marg[v], dd, list, n, with_J);
 }
 

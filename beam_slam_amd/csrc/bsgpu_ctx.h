@@ -43,6 +43,7 @@ const TypeInfo kTypes[kNumInternal] = {
     {1, 1, 7, 2, {4}},
     {6, 5, 6, 2, {4, 3, 4, 3, 1}},
     {4, 3, 6, 2, {4, 3, 1}},
+    {10, 10, 226, 15, {3, 4, 3, 3, 3, 3, 4, 3, 3, 3}},
     {4, 3, 3, 2, {4, 3, 3}},   // T_REPROJ_DENSE: idx q, p, P, (derived) camera; consts u, v, w
 };
 inline bool has_camera(int t) { return t <= 1 || t == BSGPU_F_IDP_REPROJ || t == BSGPU_F_IDP_REPROJ_UNARY || t == T_REPROJ_DENSE; }

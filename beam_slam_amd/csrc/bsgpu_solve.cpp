@@ -229,13 +229,15 @@ void eval_all(bsgpu_ctx* c, const double* x, bool with_J, int slot, const Reduce
   int marg_done = -1;
   {
     // the groups no fused launch carries: ONE launch for all of them when there are several (a pose graph's constraints + the prior on its
-    // first pose), else the group's own kernel
+    // first pose), else the group's own kernel; the unicycle factors always have their own (k_small.hip unicycle_kernel)
     SmallGroup gs[kNumInternal];
     double* ps[kNumInternal];
     int ng = 0;
+    if (c->small[BSGPU_F_UNICYCLE].n)
+      launch_small_eval(s, c->small[BSGPU_F_UNICYCLE], x, c->d_losses, with_J, cand ? c->d_small_part_cand[BSGPU_F_UNICYCLE] : c->d_small_part[BSGPU_F_UNICYCLE]);
     for (int t = 2; t < kNumInternal; ++t) {
       if (imu_pair && (t == BSGPU_F_IMU_DELTA || t == BSGPU_F_IMU_PRIOR)) continue;
-      if (t == rel_t || !c->small[t].n) continue;
+      if (t == rel_t || t == BSGPU_F_UNICYCLE || !c->small[t].n) continue;
       gs[ng] = c->small[t]; ps[ng] = cand ? c->d_small_part_cand[t] : c->d_small_part[t]; ++ng;
     }
     static const bool separate = getenv("BSGPU_EVAL_SEPARATE") != nullptr;

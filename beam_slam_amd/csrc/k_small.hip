@@ -7,12 +7,14 @@
 //   ABSPOSE     [EXT] fuse NormalPriorPose3DCostFunctor (global/absolute_pose_3d_constraint.cpp:45-50)
 //   ABS/REL_VEC3 [EXT] fuse Absolute/RelativeConstraint<V> (global/absolute_constraint.h:10-25)
 //   GRAVITY     bs_constraints/.../global/gravity_alignment_cost_functor.h:50-63
+//   UNICYCLE    bs_constraints/.../motion/unicycle_3d_state_cost_functor.h:65-125 (unicycle_body.h)             (wave / factor)
 // The reference differentiates these with ceres::AutoDiffCostFunction and multiplies by the
 // quaternion PlusJacobian; here the tangent Jacobians are closed form,
 // checked against the Jet-based oracle in tests/.
 #include "bsgpu_device.h"
 #include "reproj_body.h"
 #include "marg_body.h"
+#include "unicycle_body.h"
 
 namespace bsg {
 
@@ -284,6 +286,116 @@ __global__ __launch_bounds__(64) void imu_prior_kernel(SmallGroup g, const doubl
                                                        double* __restrict__ cost_part) {
   imu_prior_body<WITH_J>(g, blockIdx.x, x, losses, cost_part, threadIdx.x);
 }
+// ---------------------------------------------------------------------------------------------------
+// Unicycle3D kinematic constraint (unicycle_body.h): the IMU delta factor's shape, one wave per factor — lanes 0..14 own a residual
+// row, lanes 0..29 a raw tangent column; A J on the matrix core through the same LDS stage.  Its launches are its own (two factors per
+// workgroup), never a case of small_eval_set_dispatch: that kernel is at 254 VGPRs and every window would pay for one more body.
+// ---------------------------------------------------------------------------------------------------
+template <bool WITH_J>
+__device__ __forceinline__ void unicycle_body(const SmallGroup g, const int f, const double* __restrict__ x, const DevLoss* __restrict__ losses,
+                                              double* __restrict__ cost_part, const int lane, double* sB /* 16 x kImuBPitch doubles of LDS: the wave's */) {
+  constexpr int kBP = kImuBPitch;
+  const int* xo = g.xoff + (size_t)f * 10;
+  const int* to = g.toff + (size_t)f * 10;
+  const double* c = g.consts + (size_t)f * 226;
+  const double* A = c + 1;
+  double p1[3], q1[4], v1[3], w1[3], a1[3], p2[3], q2[4], v2[3], w2[3], a2[3];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { q1[k] = x[xo[1] + k]; q2[k] = x[xo[6] + k]; }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    p1[k] = x[xo[0] + k]; v1[k] = x[xo[2] + k]; w1[k] = x[xo[3] + k]; a1[k] = x[xo[4] + k];
+    p2[k] = x[xo[5] + k]; v2[k] = x[xo[7] + k]; w2[k] = x[xo[8] + k]; a2[k] = x[xo[9] + k];
+  }
+  double e[15];
+  UniLin L;
+  uni_error(p1, q1, v1, w1, a1, p2, q2, v2, w2, a2, c[0], e, &L);
+  double rk = 0.0;
+  if (lane < 15) {
+#pragma unroll
+    for (int k = 0; k < 15; ++k) rk += A[15 * lane + k] * e[k];
+  }
+  const double s = wave_sum(rk * rk);
+  double sc, cost;
+  finish_small(g, f, losses, s, &sc, &cost);
+  if (WITH_J && lane < 15) g.r[(size_t)f * 15 + lane] = rk * sc;
+  if (lane == 0) cost_part[f] = cost;
+  if (!WITH_J) return;
+  const int mn = lane & 15, mq = lane >> 4;
+  double a_op[4];
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) { const int k = 4 * kk + mq; a_op[kk] = (mn < 15 && k < 15) ? A[15 * mn + k] : 0.0; }
+  double col[15];
+#pragma unroll
+  for (int k = 0; k < 15; ++k) col[k] = 0.0;
+  if (lane < 30) uni_column(L, q1, q2, lane, col);
+  if (lane < 32) {   // (lanes 30, 31: zero columns; row 15: zero)
+#pragma unroll
+    for (int mm = 0; mm < 15; ++mm) sB[mm * kBP + lane] = col[mm];
+    sB[15 * kBP + lane] = 0.0;
+  }
+  __builtin_amdgcn_wave_barrier();
+  typedef double uni_d4 __attribute__((ext_vector_type(4)));
+  uni_d4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    const double b0 = sB[(4 * kk + mq) * kBP + mn], b1 = sB[(4 * kk + mq) * kBP + 16 + mn];
+    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a_op[kk], b0, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a_op[kk], b1, acc1, 0, 0, 0);
+  }
+  // the lane holds rows mq + 4 reg of columns mn and 16 + mn; a constant block's columns are zero
+  const double s0 = to[mn / 3] < 0 ? 0.0 : sc, s1 = (mn < 14 && to[(16 + mn) / 3] >= 0) ? sc : 0.0;
+  double* Jo = g.J + (size_t)f * 450;
+#pragma unroll
+  for (int reg = 0; reg < 4; ++reg) {
+    const int row = mq + 4 * reg;
+    if (row < 15) {
+      Jo[row * 30 + mn] = acc0[reg] * s0;
+      if (mn < 14) Jo[row * 30 + 16 + mn] = acc1[reg] * s1;
+    }
+  }
+}
+// two factors (a wave each) per 128-thread workgroup
+template <bool WITH_J>
+__device__ __forceinline__ void unicycle_unit(const SmallGroup& g, const int bx, const double* __restrict__ x, const DevLoss* __restrict__ losses,
+                                              double* __restrict__ cost_part) {
+  __shared__ double sB[WITH_J ? 2 * 16 * kImuBPitch : 1];
+  const int f = __builtin_amdgcn_readfirstlane(2 * bx + ((int)threadIdx.x >> 6));
+  if (f < g.n) unicycle_body<WITH_J>(g, f, x, losses, cost_part, threadIdx.x & 63, WITH_J ? sB + ((threadIdx.x >> 6) & 1) * 16 * kImuBPitch : sB);
+}
+template <bool WITH_J>
+__global__ __launch_bounds__(128) void unicycle_kernel(SmallGroup g, const double* __restrict__ x, const DevLoss* __restrict__ losses,
+                                                       double* __restrict__ cost_part) {
+  unicycle_unit<WITH_J>(g, (int)blockIdx.x, x, losses, cost_part);
+}
+// ... over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`; entry w is what window w's lone launch passes
+struct unicycle_eval_Args {
+  int bsg_grid;
+  SmallGroup g;
+  const double* x;
+  const DevLoss* losses;
+  double* part;
+};
+template <bool WITH_J>
+__global__ __launch_bounds__(128) void unicycle_kernel_batch(const unicycle_eval_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list) {
+  const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.y];
+  const unicycle_eval_Args& a = bsg_A[bsg_w];
+  if ((int)blockIdx.x >= a.bsg_grid) return;
+  unicycle_unit<WITH_J>(a.g, (int)blockIdx.x, a.x, a.losses, a.part);
+}
+void batchargs_unicycle_eval(BatchArgTable& t, const SmallGroup& g, const double* x, const DevLoss* losses, double* part) {
+  unicycle_eval_Args a;
+  a.g = g; a.x = x; a.losses = losses; a.part = part;
+  a.bsg_grid = (g.n + 1) / 2;
+  t.push(a);
+}
+void launch_unicycle_eval_batch(hipStream_t s, const BatchArgTable& t, const BatchDyn* dyn, int list, int n, bool with_J) {
+  if (n <= 0 || t.max_grid <= 0) return;
+  const auto* A = static_cast<const unicycle_eval_Args*>(t.dev);
+  if (with_J) hipLaunchKernelGGL(unicycle_kernel_batch<true>, dim3(t.max_grid, n), dim3(128), 0, s, A, dyn, list);
+  else hipLaunchKernelGGL(unicycle_kernel_batch<false>, dim3(t.max_grid, n), dim3(128), 0, s, A, dyn, list);
+}
+
 // both IMU factor types of a visual-inertial window (n-1 pre-integrated factors, one or two priors) in ONE launch: a launch
 // of its own for the single prior costs more in dispatch than in work (see the Makefile note on this file's flags)
 template <bool WITH_J>
@@ -1003,6 +1115,7 @@ void launch_small_eval(hipStream_t s, const SmallGroup& g, const double* x, cons
     case BSGPU_F_GRAVITY: BSG_LAUNCH(gravity_kernel, g128, 128); break;
     case BSGPU_F_IDP_REPROJ: BSG_LAUNCH2(idp_kernel, false, g128, 128); break;
     case BSGPU_F_IDP_REPROJ_UNARY: BSG_LAUNCH2(idp_kernel, true, g128, 128); break;
+    case BSGPU_F_UNICYCLE: BSG_LAUNCH(unicycle_kernel, (g.n + 1) / 2, 128); break;
     case BSGPU_F_NUM_TYPES /* internal: reprojection with a non-eliminated landmark */: BSG_LAUNCH(reproj_dense_kernel, g128, 128); break;
     default: break;
   }
@@ -1506,7 +1619,7 @@ static bool fill_small_eval_set(small_eval_set_Args& a, const SmallGroup* groups
   int blocks = 0;
   for (int i = 0; i < n_groups; ++i) {
     if (!groups[i].n) continue;
-    if (a.n == kEvalSetMax) return false;
+    if (a.n == kEvalSetMax || groups[i].type == BSGPU_F_UNICYCLE) return false;
     const bool imu = groups[i].type == BSGPU_F_IMU_DELTA || groups[i].type == BSGPU_F_IMU_PRIOR;
     a.g[a.n] = groups[i]; a.part[a.n] = parts[i]; a.first[a.n] = blocks;
     blocks += imu ? (groups[i].n + 1) / 2 : (groups[i].n + 127) / 128;
@@ -1516,7 +1629,8 @@ static bool fill_small_eval_set(small_eval_set_Args& a, const SmallGroup* groups
   a.bsg_grid = blocks;
   return true;
 }
-// false: more groups than one launch takes, or a type the launch does not carry (the caller launches them one by one)
+// false: more groups than one launch takes, or a type the launch does not carry (the caller launches them one by one; BSGPU_F_UNICYCLE
+// has launches of its own and is never handed to these)
 bool launch_small_eval_set(hipStream_t s, const SmallGroup* groups, double* const* parts, int n_groups, const double* x, const DevLoss* losses, bool with_J) {
   small_eval_set_Args a;
   if (!fill_small_eval_set(a, groups, parts, n_groups, x, losses)) return false;

@@ -1,6 +1,7 @@
 // Host-side mirrors (ROS/Eigen-free) of the variable types, ImuState and PreIntegrator the solve path
 // of the reference is written against:
-//   fuse_variables::{Orientation3DStamped, Position3DStamped, VelocityLinear3DStamped}            [EXT fuse]
+//   fuse_variables::{Orientation3DStamped, Position3DStamped, VelocityLinear3DStamped,
+//                    VelocityAngular3DStamped, AccelerationLinear3DStamped}                   [EXT fuse]
 //   bs_variables::{GyroscopeBias3DStamped, AccelerationBias3DStamped, Point3DLandmark,
 //                  Orientation3D, Position3D}        (bs_variables/include/bs_variables/*.h)
 //   bs_common::ImuState                               (bs_common/include/bs_common/imu_state.h)
@@ -158,6 +159,11 @@ BS_STAMPED_VARIABLE(fuse_variables, Orientation3DStamped, 4, 0, "fuse_variables:
 BS_STAMPED_VARIABLE(fuse_variables, Position3DStamped, 3, 1, "fuse_variables::Position3DStamped",
                     void init() {} double& x() { return data_[0]; } double& y() { return data_[1]; } double& z() { return data_[2]; })
 BS_STAMPED_VARIABLE(fuse_variables, VelocityLinear3DStamped, 3, 2, "fuse_variables::VelocityLinear3DStamped",
+                    void init() {} double& x() { return data_[0]; } double& y() { return data_[1]; } double& z() { return data_[2]; })
+// the unicycle state's angular velocity and linear acceleration (bs_models::Unicycle3D): slots after the IMU biases
+BS_STAMPED_VARIABLE(fuse_variables, VelocityAngular3DStamped, 3, 5, "fuse_variables::VelocityAngular3DStamped",
+                    void init() {} double& roll() { return data_[0]; } double& pitch() { return data_[1]; } double& yaw() { return data_[2]; })
+BS_STAMPED_VARIABLE(fuse_variables, AccelerationLinear3DStamped, 3, 6, "fuse_variables::AccelerationLinear3DStamped",
                     void init() {} double& x() { return data_[0]; } double& y() { return data_[1]; } double& z() { return data_[2]; })
 }  // namespace fuse_variables
 

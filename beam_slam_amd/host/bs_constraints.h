@@ -255,6 +255,42 @@ class GravityAlignmentStampedConstraint : public fuse_core::Constraint {
   Mat<2, 2> sqrt_information_;
 };
 
+
+// bs_constraints/src/motion/unicycle_3d_state_kinematic_constraint.cpp:11-31,73-77 — bs_models::Unicycle3D's constraint between two
+// consecutive unicycle states (unicycle_3d.cpp:256-261, covariance = process noise * dt).  dt from the position stamps; A = the upper
+// Cholesky factor of the information, covariance.inverse().llt().matrixU().  No loss (fuse_core::Constraint's default).
+class Unicycle3DStateKinematicConstraint : public fuse_core::Constraint {
+ public:
+  Unicycle3DStateKinematicConstraint(const std::string& source, const fuse_variables::Position3DStamped& position1,
+                                     const fuse_variables::Orientation3DStamped& orientation1,
+                                     const fuse_variables::VelocityLinear3DStamped& linear_velocity1,
+                                     const fuse_variables::VelocityAngular3DStamped& angular_velocity1,
+                                     const fuse_variables::AccelerationLinear3DStamped& linear_acceleration1,
+                                     const fuse_variables::Position3DStamped& position2,
+                                     const fuse_variables::Orientation3DStamped& orientation2,
+                                     const fuse_variables::VelocityLinear3DStamped& linear_velocity2,
+                                     const fuse_variables::VelocityAngular3DStamped& angular_velocity2,
+                                     const fuse_variables::AccelerationLinear3DStamped& linear_acceleration2, const Mat<15, 15>& covariance)
+      : Constraint(source, {position1.uuid(), orientation1.uuid(), linear_velocity1.uuid(), angular_velocity1.uuid(), linear_acceleration1.uuid(),
+                            position2.uuid(), orientation2.uuid(), linear_velocity2.uuid(), angular_velocity2.uuid(), linear_acceleration2.uuid()}),
+        dt_(position2.stamp() - position1.stamp()) {
+    if (!bs_math::sqrtInformationUpper(covariance, sqrt_information_)) throw std::invalid_argument("covariance is not positive definite");
+  }
+  std::string type() const override { return "bs_constraints::Unicycle3DStateKinematicConstraint"; }
+  double dt() const { return dt_; }
+  const Mat<15, 15>& sqrtInformation() const { return sqrt_information_; }
+  void pack(const BlockOf& block_of, fuse_core::FactorTables& t) const override {
+    appendBlocks(*this, block_of, t.idx[BSGPU_F_UNICYCLE]);
+    auto& c = t.consts[BSGPU_F_UNICYCLE];
+    c.push_back(dt_);
+    appendMat(c, sqrt_information_);
+    t.pushLoss(BSGPU_F_UNICYCLE, loss());
+  }
+  SharedPtr clone() const override { return std::make_shared<Unicycle3DStateKinematicConstraint>(*this); }
+ protected:
+  double dt_;
+  Mat<15, 15> sqrt_information_;
+};
 }  // namespace bs_constraints
 
 // ---------------------------------------------------------------------------------------------------

@@ -133,7 +133,7 @@ class Variable {
   // ordering keys for the deterministic block index
   virtual bool isStamped() const { return false; }
   virtual Time stamp() const { return Time(); }
-  virtual int stateSlot() const { return 99; }       // q,p,v,bg,ba = 0..4 inside one keyframe
+  virtual int stateSlot() const { return 99; }       // q,p,v,bg,ba = 0..4 inside one keyframe (a unicycle state's w, a: 5, 6)
   virtual bool isLandmark() const { return false; }
   virtual uint64_t landmarkId() const { return 0; }
   virtual void print(std::ostream& s) const {

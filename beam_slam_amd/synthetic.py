@@ -360,6 +360,84 @@ def vio_window(n_kf=200, n_lm=50000, seed=20250620, kf_rate=10.0, imu_rate=200.0
     return pr
 
 
+# ---------------------------------------------------------------------------------------------
+# Unicycle3D window: bs_models::Unicycle3D's kinematic constraints between consecutive states (unicycle_3d.cpp:256-261) — a motion-model
+# chain, or the standalone-VO local graph with them in place of the IMU factors (visual_odometry.cpp:838-905)
+# ---------------------------------------------------------------------------------------------
+UNICYCLE_SIGMA = np.array([0.05] * 3 + [0.02] * 3 + [0.1] * 3 + [0.05] * 3 + [0.5] * 3)   # process-noise std per unit time
+
+
+def unicycle_process_cov(rng=None, dense=False):
+    """15x15 process-noise covariance (p, rpy, v, w, a): diagonal, or seeded with correlations (dense=True)."""
+    D = np.diag(UNICYCLE_SIGMA)
+    if not dense:
+        return D @ D
+    B = rng.normal(0, 0.3, (15, 15))
+    C = B @ B.T + np.eye(15)
+    d = 1.0 / np.sqrt(np.diag(C))
+    return D @ (C * np.outer(d, d)) @ D
+
+
+def unicycle_window(n_states=200, n_lm=0, seed=20251016, dt=0.1, dense_cov=False, perturb=True, sigma_rot=0.02, sigma_pos=0.05,
+                    sigma_rate=0.05):
+    """n_states on the Lissajous path, each (p, q, v_linear, v_angular, a_linear) — v, w and a in the body frame, as the unicycle
+    prediction reads them — chained by BSGPU_F_UNICYCLE factors (consts dt, A = sqrt information of cov * dt), with a prior on the
+    whole first state: a pose prior (ABSPOSE) and ABS_VEC3 priors on v, w, a (without them the chain leaves those nine free), and
+    without landmarks a noisy pose measurement (ABSPOSE) of every later state.
+    n_lm > 0: vio_window's visual factors and landmarks (with_imu=False) on the same states: the standalone-VO local graph.
+    perturb=False: every state starts on the path.  Blocks are added per state as q, p, v, w, a (vio_window's order)."""
+    rng = np.random.default_rng(seed)
+    traj = Lissajous(duration=n_states * dt)
+    t = np.arange(n_states) * dt
+    R_true = np.stack([traj.rot(s) for s in t])
+    q_true = np.stack([rot_to_quat(R) for R in R_true])
+    p_true = np.stack([traj.pos(s) for s in t])
+    v_true = np.einsum('nji,nj->ni', R_true, np.stack([traj.vel(s) for s in t]))
+    w_true = np.stack([traj.omega_body(s) for s in t])
+    a_true = np.einsum('nji,nj->ni', R_true, np.stack([traj.acc(s) for s in t]))
+    if n_lm > 0:
+        pr = vio_window(n_kf=n_states, n_lm=n_lm, seed=seed, kf_rate=1.0 / dt, with_imu=False, first_prior=False)
+        kf = pr.meta["kf_blocks"]
+        vals = pr.values.copy()
+        for i in range(n_states):
+            for b, v in zip(kf[i, 2:], (v_true[i], w_true[i], a_true[i])):
+                vals[pr.offset[b]:pr.offset[b] + 3] = v + (rng.normal(0, sigma_rate, 3) if perturb else 0.0)
+            if not perturb:
+                vals[pr.offset[kf[i, 0]]:pr.offset[kf[i, 0]] + 4] = q_true[i]
+                vals[pr.offset[kf[i, 1]]:pr.offset[kf[i, 1]] + 3] = p_true[i]
+        pr.values = vals
+    else:
+        pr = Problem()
+        kf = np.empty((n_states, 5), np.int32)
+        for i in range(n_states):
+            e = (lambda s: rng.normal(0, s, 3)) if perturb else (lambda s: 0.0)
+            kf[i, 0] = pr.add_quat(_perturb_quat(q_true[i], rng, sigma_rot) if perturb else q_true[i])
+            kf[i, 1] = pr.add_block(p_true[i] + e(sigma_pos))
+            kf[i, 2] = pr.add_block(v_true[i] + e(sigma_rate))
+            kf[i, 3] = pr.add_block(w_true[i] + e(sigma_rate))
+            kf[i, 4] = pr.add_block(a_true[i] + e(sigma_rate))
+    cov = unicycle_process_cov(rng, dense_cov)
+    A = sqrt_information_upper(cov * dt)
+    if n_states > 1:
+        idx = np.concatenate([kf[:-1][:, [1, 0, 2, 3, 4]], kf[1:][:, [1, 0, 2, 3, 4]]], axis=1)
+        pr.add_factors(capi.F_UNICYCLE, idx, np.tile(np.concatenate([[dt], A.ravel()]), (n_states - 1, 1)))
+    if n_lm == 0 and n_states > 1:
+        # without landmarks, a pose measurement of every later state (a GPS / odometry source) keeps the system over-determined
+        Ap = sqrt_information_upper(np.diag([0.1 ** 2] * 3 + [0.02 ** 2] * 3))
+        meas = [np.concatenate([p_true[i] + rng.normal(0, 0.1, 3), _perturb_quat(q_true[i], rng, 0.02), Ap.ravel()]) for i in range(1, n_states)]
+        pr.add_factors(capi.F_ABSPOSE, kf[1:][:, [1, 0]], np.stack(meas))
+    vals = pr.values
+    b = np.concatenate([pr.block(int(kf[0, 1]), vals), pr.block(int(kf[0, 0]), vals)])
+    pr.add_factors(capi.F_ABSPOSE, [[kf[0, 1], kf[0, 0]]], [np.concatenate([b, sqrt_information_upper(1e-4 * np.eye(6)).ravel()])])
+    A3 = sqrt_information_upper(1e-2 * np.eye(3))
+    pr.add_factors(capi.F_ABS_VEC3, kf[0, 2:, None], [np.concatenate([pr.block(int(bb), vals), A3.ravel()]) for bb in kf[0, 2:]])
+    meta = dict(pr.meta)
+    meta.update(kind="unicycle_window", n_states=n_states, n_lm=n_lm, seed=seed, dt=dt, kf_blocks=kf, cov=cov, q_true=q_true,
+                p_true=p_true, v_true=v_true, w_true=w_true, a_true=a_true)
+    pr.meta = meta
+    return pr
+
+
 def c1(seed=20250620):
     """BASELINE config 1: 20 keyframes x 500 landmarks (plumbing case)."""
     return vio_window(n_kf=20, n_lm=500, seed=seed)

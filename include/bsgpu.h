@@ -147,7 +147,16 @@ enum {
    *   The observation in the anchor frame: the residual is constant in every
    *   block (zero Jacobian), it only contributes to the cost.                  */
   BSGPU_F_IDP_REPROJ_UNARY = 11,
-  BSGPU_F_NUM_TYPES = 12
+  /* bs_constraints::Unicycle3DStateKinematicConstraint
+   *   (motion/unicycle_3d_state_cost_functor.h:65-125, unicycle_3d_predict.h:49-196,
+   *    src/motion/unicycle_3d_state_kinematic_constraint.cpp:11-31,73-77; AutoDiff<15, 3,4,3,3,3, 3,4,3,3,3>)
+   *   idx   : (p, q, v_linear, v_angular, a_linear)_1, (p, q, v_linear, v_angular, a_linear)_2
+   *   consts: dt (= stamp2 - stamp1), A[225] (15x15 row-major = covariance.inverse().llt().matrixU())
+   *   r = A [p2 - p^; wrap(rpy(q2) - rpy^); v2 - v^; w2 - w^; a2 - a^] with the unicycle prediction
+   *   (p^, rpy^, v^, w^, a^) of state 1 over dt; rpy(q): fuse_core getRoll/getPitch/getYaw of the stored q.
+   *   bs_models::Unicycle3D (unicycle_3d.cpp:256-261) emits it with covariance process_noise * dt.              */
+  BSGPU_F_UNICYCLE = 12,
+  BSGPU_F_NUM_TYPES = 13
 };
 
 /* number of int32 per factor in block_idx / doubles per factor in consts /
