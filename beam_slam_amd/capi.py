@@ -30,6 +30,7 @@ F_UNICYCLE = 12
 F_NUM_TYPES = 13
 
 LINEAR_AUTO, LINEAR_SCHUR_CHOLESKY, LINEAR_PCG, LINEAR_SCHUR_PCG = 0, 1, 2, 3
+TR_LEVENBERG_MARQUARDT, TR_DOGLEG, TR_SUBSPACE_DOGLEG = 0, 1, 2
 CONVERGENCE, NO_CONVERGENCE, FAILURE = 0, 1, 2
 
 
@@ -50,7 +51,7 @@ class Options(C.Structure):
         ("min_lm_diagonal", C.c_double),
         ("max_lm_diagonal", C.c_double),
         ("pcg_max_iterations", C.c_int32),
-        ("reserved0", C.c_int32),
+        ("trust_region_strategy_type", C.c_int32),
         ("pcg_tolerance", C.c_double),
     ]
 
@@ -113,7 +114,7 @@ SYMBOLS = [
     "evaluate", "num_residuals", "num_parameters_tangent", "tangent_offset", "covariance", "marginalize", "get_marginal",
     "reprojection_errors", "preintegrate", "triangulate", "time_reproj_jacobian_ms", "reproj_jacobian_bytes", "dense_solve", "plan_info",
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
-    "covariance_requests", "localize_frames",
+    "covariance_requests", "localize_frames", "num_factorizations",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -405,6 +406,14 @@ class Solver:
 
     def reset_values(self):
         self._chk(self._f("reset_values")(self._ctx))
+
+    def num_factorizations(self):
+        """Linear systems the last solve assembled and solved (bsgpu_num_factorizations): every Gauss-Newton / LM attempt, DOGLEG's mu
+        retries included; a DOGLEG step that reuses its Gauss-Newton step after a rejection does not count."""
+        fn = self._f("num_factorizations")
+        fn.argtypes = [C.c_void_p]
+        fn.restype = C.c_int
+        return fn(self._ctx)
 
     def iterations(self):
         n = self._f("num_iterations_recorded")(self._ctx)

@@ -461,6 +461,7 @@ int bsgpu_reset_values(bsgpu_ctx* c) try {
   return BSGPU_OK;
 } catch (...) { return api_exception(c); }
 int bsgpu_num_iterations_recorded(const bsgpu_ctx* c) { return c ? (int)c->iters.size() : 0; }
+int bsgpu_num_factorizations(const bsgpu_ctx* c) { return c ? c->num_factorizations : 0; }
 int bsgpu_get_iteration(const bsgpu_ctx* c, int32_t i, bsgpu_iteration* out) try {
   if (!c) return BSGPU_ERR_INVALID;
   if (i < 0 || i >= (int)c->iters.size() || !out) return BSGPU_ERR_INVALID;
@@ -1067,6 +1068,8 @@ int bsgpu_localize_frames(bsgpu_ctx* c, int32_t n_frames, const int32_t* obs_sta
   if (n_frames < 0 || !obs_start || !camera || !q_init || !p_init || !options || !q_out || !p_out || !status)
     return fail(c, BSGPU_ERR_INVALID, "localize_frames: null argument");
   if ((points == nullptr) == (lm_block == nullptr)) return fail(c, BSGPU_ERR_INVALID, "localize_frames: pass exactly one of points and lm_block");
+  if (options->trust_region_strategy_type != BSGPU_TR_LEVENBERG_MARQUARDT)
+    return fail(c, BSGPU_ERR_UNSUPPORTED, "localize_frames: its in-kernel loop is Levenberg-Marquardt only (trust_region_strategy_type must be 0)");
   if (loss_kind < BSGPU_LOSS_TRIVIAL || loss_kind > BSGPU_LOSS_HUBER) return fail(c, BSGPU_ERR_INVALID, "unknown loss kind");
   if (obs_start[0] != 0) return fail(c, BSGPU_ERR_INVALID, "localize_frames: obs_start[0] must be 0");
   for (int f = 0; f < n_frames; ++f) {

@@ -69,6 +69,7 @@ bool shape_of(const bsgpu_ctx* c, WinShape& w) {
 bool batch_covers(bsgpu_ctx* c, const bsgpu_options& o) {
   if (!c->finalized) return false;
   if (!(o.linear_solver_type == BSGPU_LINEAR_AUTO || o.linear_solver_type == BSGPU_LINEAR_SCHUR_CHOLESKY)) return false;
+  if (o.trust_region_strategy_type != BSGPU_TR_LEVENBERG_MARQUARDT) return false;   // (DOGLEG: bsgpu_solve on a thread of its own)
   if (!c->dense_ok || c->use_graphs || !c->d_S || !c->h_scal_dev || !c->d_reduce_counter || c->n_reduce <= 0 || c->n_pose <= 0) return false;
   {   // at most ONE dense prior with free blocks (a window after a slide with true marginalisation), narrow enough for the one-launch evaluation
     int n_act = 0;
@@ -487,6 +488,7 @@ bool solve_batched(bsgpu_ctx* const* ctxs, const int* idx, int m, const bsgpu_op
     if (hipStreamQuery(c->stream) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(c->stream); }
     L[i].lm.start(&o[options_stride ? idx[i] : 0], &s[idx[i]], &c->iters, c->n_tan, c->n_res, BSGPU_LINEAR_SCHUR_CHOLESKY);
     c->use_pcg = false; c->use_spcg = false; c->spec_J = false; c->cost_x_stale = false; c->pre_cleared = false;
+    c->num_factorizations = 0;
     act.push_back(i);
   }
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -506,6 +508,7 @@ bool solve_batched(bsgpu_ctx* const* ctxs, const int* idx, int m, const bsgpu_op
   int64_t rounds = 0;
   while (!act.empty()) {
     ++rounds;
+    for (int w : act) if (first || !L[w].lm.grad_only) ++L[w].c->num_factorizations;   // (bsgpu_num_factorizations: every step this round computes)
     enqueue_round(P, L, act);
     err = wait_round(P, L, act);
     if (err != BSGPU_OK) break;

@@ -261,6 +261,10 @@ struct bsgpu_ctx {
   GradNormRide gn_ride;
   bool spec_J = false;   // residuals + Jacobians currently hold the CANDIDATE's (evaluated ahead of the accept/reject decision)
   int nbr = 0, nblk = 0, pcg_iters_total = 0;
+  int num_factorizations = 0;    // linear systems the last solve assembled and solved (bsgpu_num_factorizations)
+  // DOGLEG (bsgpu_solve.cpp solve_dogleg, k_dogleg.hip): g = J^T r, v = g / c, the Gauss-Newton step — kept between a rejection and its reuse —,
+  // the per-workgroup partials of the reductions and their sums (allocated on first use after a finalize)
+  double *d_dl_g = nullptr, *d_dl_v = nullptr, *d_dl_gn = nullptr, *d_dl_part = nullptr, *d_dl_scal = nullptr;
   PcgPersistDev pcg_persist;     // G = 0: the launch-per-iteration path only
   int *d_row_ptr = nullptr, *d_col = nullptr, *d_diag_slot = nullptr, *d_pair_slot = nullptr;
   int* d_slots[kNumInternal] = {nullptr};
@@ -324,6 +328,7 @@ struct bsgpu_ctx {
     idp = IdpElim();
     for (auto& g : small) g = SmallGroup();
     d_x = d_xcand = d_x0 = nullptr;
+    d_dl_g = d_dl_v = d_dl_gn = d_dl_part = d_dl_scal = nullptr;
     bsr_built = false; spcg_built = false;
     destroy_graphs();
   }
@@ -352,6 +357,7 @@ int build_bsr(bsgpu_ctx* c);
 int build_spcg(bsgpu_ctx* c);
 // bsgpu_solve.cpp
 int solve(bsgpu_ctx* c, const bsgpu_options& o, bsgpu_summary& sum);
+int check_strategy(bsgpu_ctx* c, const bsgpu_options& o);   // trust_region_strategy_type against the problem and the other options
 void enqueue_fixed_cost(bsgpu_ctx* c, hipStream_t s);
 void eval_all(bsgpu_ctx* c, const double* x, bool with_J, int slot, const ReduceRide* red = nullptr);
 // factor_follows: linear_solve_and_candidate() comes next — its factorisation launch may then carry the LM diagonal and the gradient norms

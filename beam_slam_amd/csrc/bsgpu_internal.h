@@ -598,6 +598,15 @@ void launch_update(hipStream_t s, int nb, const int* blk_xoff, const int* blk_to
                    double* part /* 2 * nblocks_grid */, int* n_part);
 void launch_sum(hipStream_t s, const double* part, int n, double* out, int accumulate);
 void launch_zero(hipStream_t s, double* p, int64_t n);
+// k_dogleg.hip: the vector work of a DOGLEG step (dogleg.h); every launch ends in a one-workgroup sum of its partials into `out`
+void launch_dl_vec(hipStream_t s, int n_tan, const double* g, const double* dcl, const double* delta_gn, double* v, double* gn_keep, double* part,
+                   double* out3 /* |g'|^2, |gn'|^2, g'.gn' */);
+void launch_dl_step(hipStream_t s, int n_tan, const double* v, const double* gn, double a, double b, const double* dcl, double* delta, double* part,
+                    double* out1 /* |step'|^2 */);
+int dl_jv_records(const Visual& vis, const SmallGroup* small, int n_small, const MargDev* marg, int n_marg);   // partial records launch_dl_jv writes
+void launch_dl_jv(hipStream_t s, const Visual& vis, int n_pose, const SmallGroup* small, int n_small, const MargDev* marg, int n_marg, const double* u,
+                  double* part, double* out2 /* |J u|^2, (J u).r */);
+void launch_dl_sum(hipStream_t s, const double* part, int n, int k, double* out);
 void launch_zero4(hipStream_t s, double* p0, int64_t n0, double* p1, int64_t n1, double* p2, int64_t n2, double* p3, int64_t n3);
 void launch_zero_tiles_multi(hipStream_t s, double* S, int ld, const int* tiles_dev, int n_tiles, double* a, int na, double* b, int nb, double* c,
                              int nc, double* radius_slot, double radius);

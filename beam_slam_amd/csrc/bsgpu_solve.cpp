@@ -818,6 +818,168 @@ void enqueue_fixed_cost(bsgpu_ctx* c, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// [EXT] ceres::internal::TrustRegionMinimizer + DoglegStrategy (TRADITIONAL_DOGLEG), restated: the strategy's arithmetic is dogleg.h, the
+// minimiser around it LmState (lm_state.h, its DOGLEG branch).  Host-decided and eager: no assembly ahead, no decision on the device, no graph
+// capture.  A Gauss-Newton solve is the LM step at radius 1 / mu — assemble -> factorise -> back-substitute unchanged — followed by the
+// vector work of k_dogleg.hip; a step after a rejection reuses it: one evaluation at x (the Jacobians the J delta pass reads), the step's
+// vector, its J delta, the candidate and its cost.
+// ---------------------------------------------------------------------------------------------------
+// trust_region_strategy_type against what the problem and the other options allow (bsgpu_solve, bsgpu_solve_batch); after finalize()
+int check_strategy(bsgpu_ctx* c, const bsgpu_options& o) {
+  const int t = o.trust_region_strategy_type;
+  if (t == BSGPU_TR_LEVENBERG_MARQUARDT) return BSGPU_OK;
+  if (t == BSGPU_TR_SUBSPACE_DOGLEG) return fail(c, BSGPU_ERR_UNSUPPORTED, "trust_region_strategy_type SUBSPACE_DOGLEG is not implemented (DOGLEG is TRADITIONAL_DOGLEG)");
+  if (t != BSGPU_TR_DOGLEG) return fail(c, BSGPU_ERR_INVALID, "trust_region_strategy_type: not a BSGPU_TR_* value");
+  if (o.linear_solver_type == BSGPU_LINEAR_PCG || o.linear_solver_type == BSGPU_LINEAR_SCHUR_PCG)
+    return fail(c, BSGPU_ERR_INVALID, "DOGLEG needs an exact factorisation-based linear solver: not BSGPU_LINEAR_PCG / BSGPU_LINEAR_SCHUR_PCG");
+  if (!c->dense_ok)
+    return fail(c, BSGPU_ERR_UNSUPPORTED, "DOGLEG: the reduced system is above the exact path's limit (BSGPU_LINEAR_AUTO would take the block-sparse PCG)");
+  if (c->idp.n_lm > 0 || c->small[BSGPU_F_IDP_REPROJ].n > 0 || c->small[BSGPU_F_IDP_REPROJ_UNARY].n > 0)
+    return fail(c, BSGPU_ERR_UNSUPPORTED, "DOGLEG: inverse-depth factors (types 10 and 11) are not supported");
+  return BSGPU_OK;
+}
+
+namespace {
+// the sums of k_dogleg.hip's launches, d_dl_scal
+enum { DL_G2 = 0, DL_GN2 = 1, DL_GGN = 2, DL_JV2 = 3, DL_JVR = 4, DL_S2 = 5, DL_JD2 = 6, DL_JDR = 7, DL_STEP2 = 8, DL_X2 = 9, DL_NUM = 10 };
+}
+
+static int solve_dogleg(bsgpu_ctx* c, const bsgpu_options& o, bsgpu_summary& sum, std::chrono::steady_clock::time_point t_start, hipEvent_t ev0,
+                        hipEvent_t ev1) {
+  hipStream_t s = c->stream;
+  const int n_tan = c->n_tan;
+  std::vector<SmallGroup> groups;
+  std::vector<MargDev> margs;
+  for (int t = 2; t < kNumInternal; ++t) if (c->small[t].n) groups.push_back(c->small[t]);
+  for (const auto& mc : c->marg) if (mc.active && mc.dev.rows > 0) margs.push_back(mc.dev);
+  const int n_jv = dl_jv_records(c->vis, groups.data(), (int)groups.size(), margs.data(), (int)margs.size());
+  if (!c->d_dl_g) {   // (device buffers of this finalize: free_device forgets them)
+    const size_t n_part = std::max<size_t>({(size_t)2 * n_jv, (size_t)3 * ((n_tan + 255) / 256), (size_t)2 * ((c->nb + 255) / 256), 1});
+    c->d_dl_g = c->alloc<double>(n_tan); c->d_dl_v = c->alloc<double>(n_tan); c->d_dl_gn = c->alloc<double>(n_tan);
+    c->d_dl_part = c->alloc<double>(n_part); c->d_dl_scal = c->alloc<double>(DL_NUM);
+    if (!c->d_dl_g || !c->d_dl_v || !c->d_dl_gn || !c->d_dl_part || !c->d_dl_scal) {
+      c->d_dl_g = c->d_dl_v = c->d_dl_gn = c->d_dl_part = c->d_dl_scal = nullptr;
+      return fail(c, BSGPU_ERR_DEVICE, "DOGLEG: device memory for the step's vectors");
+    }
+  }
+  const bool graphs = c->use_graphs;
+  c->use_graphs = false;   // (eager launches; restored below)
+  c->spec_J = false; c->spec_cand_arrays = false; c->xpart_stale = false; c->cost_x_stale = false;
+  // (a replayed LM step leaves the reduced system as it is and does not say so: the first assembly clears it itself)
+  c->pre_cleared = false;
+  double dl[DL_NUM];
+  auto fetch_all = [&]() -> int {
+    int rc = fetch_scalars(c);
+    if (rc != BSGPU_OK) return rc;
+    HIPCHK(c, hipMemcpyAsync(dl, c->d_dl_scal, sizeof(dl), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return BSGPU_OK;
+  };
+
+  LmState lm;
+  const bsgpu_summary head = sum;
+  lm.start(&o, &sum, &c->iters, head.num_parameters_tangent, head.num_residuals, head.linear_solver_used);
+  lm.t_start = t_start;
+  double h[SC_NUM];
+  DoglegVecs w;                       // of the current linearisation
+  double cost_x = 0.0, gmax = 0.0, gn2 = 0.0;   // ... its cost and gradient norms
+  bool first_asm = true, begun = false;
+  int rc = BSGPU_OK;
+  for (;;) {
+    const int kind = begun ? lm.kind : STEP_FIRST;
+    // the accepted candidate becomes the current point by a copy, not by swapping the two buffers: LM steps captured as hipGraphs (BSGPU_GRAPH)
+    // hold both pointers frozen, and the batched solve's tables name them too
+    if (kind == STEP_ACCEPT) launch_copy(s, c->d_xcand, c->d_x, (int64_t)c->h_x.size(), 0);
+    // the Jacobians at x: new after an accepted step; restored for a step at the same point (the candidate's evaluation may have overwritten the
+    // residuals the J delta pass reads)
+    eval_all(c, c->d_x, true, SC_COST_X);
+    bool valid = true;
+    if (begun && lm.grad_only) {   // (the iteration budget is used up: the accepted point's cost and gradient only)
+      assemble(c, o, 1.0 / lm.mu, true, false, /*gradient_only=*/true, /*factor_follows=*/true);
+      final_reduce(c);
+      if ((rc = fetch_all()) != BSGPU_OK) break;
+      std::memcpy(h, c->h_scal, sizeof(h));
+      lm.advance(h, false, false);
+      if (lm.done) break;
+      continue;
+    }
+    if (kind != STEP_REUSE) {
+      // a new Gauss-Newton step: mu retries while the factorisation fails ([EXT] DoglegStrategy::ComputeGaussNewtonStep)
+      valid = false;
+      bool have_scalars = false;
+      while (lm.mu < kDoglegMaxMu) {
+        assemble(c, o, 1.0 / lm.mu, true, first_asm, false, /*factor_follows=*/true);
+        first_asm = false;
+        launch_copy(s, c->d_grad, c->d_dl_g, n_tan, 0);   // (J^T r: the linear solve's last launch may clear it for the next assembly)
+        linear_solve_and_candidate(c, o, false, /*skip_cand_cost=*/true);
+        ++c->num_factorizations;
+        launch_dl_vec(s, n_tan, c->d_dl_g, c->d_dcl, c->d_delta, c->d_dl_v, c->d_dl_gn, c->d_dl_part, c->d_dl_scal + DL_G2);
+        launch_dl_jv(s, c->vis, c->n_pose, groups.data(), (int)groups.size(), margs.data(), (int)margs.size(), c->d_dl_v, c->d_dl_part, c->d_dl_scal + DL_JV2);
+        if ((rc = fetch_all()) != BSGPU_OK) break;
+        have_scalars = true;
+        cost_x = c->h_scal[SC_COST_X]; gmax = c->h_scal[SC_GRAD_MAX]; gn2 = c->h_scal[SC_GRAD_NORM2];
+        if (!begun) lm.fixed = c->any_inactive ? c->h_scal[SC_FIXED_COST] : 0.0;
+        if (c->h_scal[SC_CHOL_FAIL] == 2.0 && c->d_ftasks) {
+          // a wait inside the single-launch factorisation timed out (the GPU is shared): not a numerical failure — the launch-per-step path from
+          // here on (captured LM steps hold the single-launch kernel: they go, and the next LM solve captures again), and the same solve again,
+          // counted once
+          c->d_ftasks = nullptr;
+          if (graphs) c->destroy_graphs();
+          --c->num_factorizations;
+          continue;
+        }
+        if (!(c->h_scal[SC_CHOL_FAIL] > 0.0) && std::isfinite(dl[DL_GN2])) { valid = true; break; }
+        if (!dl_retry(&lm.mu)) break;
+      }
+      if (rc != BSGPU_OK) break;
+      if (!have_scalars) {   // (mu >= 1: Ceres does not try; the point's cost and gradient all the same)
+        assemble(c, o, 1.0, true, first_asm, /*gradient_only=*/true, true);
+        first_asm = false;
+        final_reduce(c);
+        if ((rc = fetch_all()) != BSGPU_OK) break;
+        cost_x = c->h_scal[SC_COST_X]; gmax = c->h_scal[SC_GRAD_MAX]; gn2 = c->h_scal[SC_GRAD_NORM2];
+        if (!begun) lm.fixed = c->any_inactive ? c->h_scal[SC_FIXED_COST] : 0.0;
+      }
+      if (valid) { w.g2 = dl[DL_G2]; w.gn2 = dl[DL_GN2]; w.ggn = dl[DL_GGN]; w.jv2 = dl[DL_JV2]; }
+    }
+    std::memset(h, 0, sizeof(h));
+    h[SC_COST_X] = cost_x; h[SC_GRAD_MAX] = gmax; h[SC_GRAD_NORM2] = gn2;
+    if (valid) {
+      const DoglegStep st = dl_coefficients(w, lm.radius);
+      launch_dl_step(s, n_tan, c->d_dl_v, c->d_dl_gn, st.a, st.b, c->d_dcl, c->d_delta, c->d_dl_part, c->d_dl_scal + DL_S2);
+      launch_dl_jv(s, c->vis, c->n_pose, groups.data(), (int)groups.size(), margs.data(), (int)margs.size(), c->d_delta, c->d_dl_part, c->d_dl_scal + DL_JD2);
+      int n_part = 0;
+      launch_update(s, c->nb, c->d_blk_xoff, c->d_blk_toff, c->d_blk_size, c->d_blk_manifold, c->d_x, c->d_delta, c->d_xcand, c->d_dl_part, &n_part);
+      launch_dl_sum(s, c->d_dl_part, n_part, 2, c->d_dl_scal + DL_STEP2);
+      eval_all(c, c->d_xcand, false, SC_COST_CAND);
+      final_reduce(c);
+      if ((rc = fetch_all()) != BSGPU_OK) break;
+      h[SC_COST_CAND] = c->h_scal[SC_COST_CAND];
+      h[SC_MCC] = -(dl[DL_JDR] + 0.5 * dl[DL_JD2]);   // -(J delta).(r + J delta / 2), summed as its two parts
+      h[SC_STEP_NORM2] = dl[DL_STEP2]; h[SC_X_NORM2] = dl[DL_X2];
+      lm.dl_step_norm = st.norm_is_measured ? std::sqrt(dl[DL_S2]) : st.norm;
+    } else {
+      h[SC_CHOL_FAIL] = 1.0;   // (LmState: an invalid step)
+    }
+    if (!begun) { begun = true; lm.begin(h, lm.fixed, false); }
+    else lm.advance(h, false, false);
+    if (lm.done) break;
+  }
+  c->use_graphs = graphs;
+  c->pre_cleared = false;
+  if (rc != BSGPU_OK) return rc;
+  HIPCHK(c, hipEventRecord(ev1, s));
+  HIPCHK(c, hipEventSynchronize(ev1));
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, ev0, ev1);
+  sum.device_time_in_seconds = ms * 1e-3;
+  c->scal_mirrored = false; c->ev_reduce_pending = false; c->spec_J = false; c->spec_lm_radius = 0.0; c->spec_dirty = false; c->spec_dev = false;
+  sum.num_inner_iterations = 0;
+  sum.total_time_in_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+  return BSGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
 // [EXT] ceres::internal::TrustRegionMinimizer + LevenbergMarquardtStrategy, restated
 // ---------------------------------------------------------------------------------------------------
 constexpr int kAssemblyAheadMaxResiduals = 400000;   // ... and residual rows in all (C3: 121 500; C2: 804 000)
@@ -826,8 +988,10 @@ int solve(bsgpu_ctx* c, const bsgpu_options& o, bsgpu_summary& sum) {
   using clk = std::chrono::steady_clock;
   const auto t_start = clk::now();
   auto elapsed = [&]() { return std::chrono::duration<double>(clk::now() - t_start).count(); };
+  c->num_factorizations = 0;   // (a solve that is refused reports none)
   int rc = finalize(c);
   if (rc != BSGPU_OK) return rc;
+  if ((rc = check_strategy(c, o)) != BSGPU_OK) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   std::memset(&sum, 0, sizeof(sum));
   c->iters.clear();
@@ -852,6 +1016,7 @@ int solve(bsgpu_ctx* c, const bsgpu_options& o, bsgpu_summary& sum) {
   // iteration zero
   double fixed = 0.0;
   enqueue_fixed_cost(c, s);
+  if (o.trust_region_strategy_type == BSGPU_TR_DOGLEG) return solve_dogleg(c, o, sum, t_start, ev0, ev1);
   build_graphs(c, o);
   // the trust-region loop itself: lm_state.h (one copy, shared with bsgpu_solve_batch); this driver computes the steps it asks for
   LmState lm;
@@ -885,6 +1050,7 @@ int solve(bsgpu_ctx* c, const bsgpu_options& o, bsgpu_summary& sum) {
     return (lm_ahead && guess_held && !c->use_graphs && !c->use_pcg) ? guessed : 0.0;
   };
   run_step(c, o, STEP_FIRST, lm.radius, false, radius_ahead(lm.radius), lm_dev ? &lmd : nullptr);
+  ++c->num_factorizations;
   rc = fetch_scalars(c);
   if (rc != BSGPU_OK) { (void)pcg_check(c); return rc; }
   bool pcg_redo = !pcg_check(c);
@@ -910,6 +1076,7 @@ int solve(bsgpu_ctx* c, const bsgpu_options& o, bsgpu_summary& sum) {
                              (rel_prev > 0.0 && rel_last * std::min(1.0, rel_last / rel_prev) < 4.0 * o.function_tolerance);
     lmd.x_cost = lm.kind == STEP_REJECT ? lm.x_cost : lm.cand_cost;   // (the cost at the point this step is computed at, where the host holds it: enqueue_step)
     run_step(c, o, lm.kind, lm.radius, lm.grad_only, (lm.grad_only || likely_last) ? 0.0 : radius_ahead(lm.radius), lm_dev ? &lmd : nullptr);
+    if (!lm.grad_only && !lm.retry_timeout) ++c->num_factorizations;   // (a step computed again after a time-out is counted once)
     rc = fetch_scalars(c);
     if (rc != BSGPU_OK) { (void)pcg_check(c); return rc; }
     pcg_redo = !pcg_check(c);

@@ -18,11 +18,14 @@
 
 #include "../../include/bsgpu.h"
 #include "bsgpu_internal.h"
+#include "dogleg.h"
 #include "lm_decide.h"
 
 namespace bsg {
 
-enum StepKind { STEP_FIRST = 0, STEP_ACCEPT = 1, STEP_REJECT = 2 };
+// STEP_REUSE (DOGLEG only): the step again at the same point and a new radius from the Gauss-Newton step and Cauchy point already computed —
+// no assembly, no factorisation
+enum StepKind { STEP_FIRST = 0, STEP_ACCEPT = 1, STEP_REJECT = 2, STEP_REUSE = 3 };
 
 struct LmState {
   const bsgpu_options* o = nullptr;
@@ -36,6 +39,10 @@ struct LmState {
   int kind = STEP_FIRST;      // the step the driver is asked to compute next
   bool grad_only = false;     // ... without a linear solve: the iteration budget is used up, only the accepted point's cost and gradient are wanted
   std::chrono::steady_clock::time_point t_start;
+  // the strategy (bsgpu_options::trust_region_strategy_type).  DOGLEG (dogleg.h): `radius` is the dogleg radius, `mu` the regularisation of
+  // its Gauss-Newton solve; the driver sets dl_step_norm (|step'|) before advance() looks at the step
+  bool dogleg = false;
+  double mu = kDoglegMinMu, dl_step_norm = 0.0;
 
   double elapsed() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); }
   void request(int k, bool g) { kind = k; grad_only = g; absorb = true; }
@@ -47,6 +54,7 @@ struct LmState {
     sum->num_parameters_tangent = n_tan; sum->num_residuals = n_res;
     sum->linear_solver_used = linear_solver_used;
     radius = o->initial_trust_region_radius; decrease_factor = 2.0;
+    dogleg = o->trust_region_strategy_type == BSGPU_TR_DOGLEG; mu = kDoglegMinMu; dl_step_norm = 0.0;
     kind = STEP_FIRST; grad_only = false; absorb = false; done = false; retry_timeout = false;
     msg = "";
     t_start = std::chrono::steady_clock::now();
@@ -115,7 +123,8 @@ struct LmState {
           msg = "Number of consecutive invalid steps more than max_num_consecutive_invalid_steps.";
           break;
         }
-        radius *= 0.5;   // [EXT] LevenbergMarquardtStrategy::StepIsInvalid(): the radius is halved, decrease_factor_ is untouched
+        if (dogleg) dl_step_invalid(&mu);   // [EXT] DoglegStrategy::StepIsInvalid(): mu *= 10, a new solve at the same radius
+        else radius *= 0.5;   // [EXT] LevenbergMarquardtStrategy::StepIsInvalid(): the radius is halved, decrease_factor_ is untouched
         it.cost = x_cost + fixed; it.step_is_successful = 0;
         if (it.iteration >= o->max_num_iterations) continue;   // the loop ends at its top: a step from here would never be looked at
         request(STEP_REJECT, false);
@@ -132,8 +141,11 @@ struct LmState {
       it.relative_decrease = (x_cost - cand_cost) / mcc;
       const bool last_iteration = it.iteration >= o->max_num_iterations;
       if (it.relative_decrease > o->min_relative_decrease) {
-        radius = radius / std::max(1.0 / 3.0, 1.0 - lm_cube(2.0 * it.relative_decrease - 1.0));   // ([EXT] pow(2 rho - 1, 3): lm_decide.h lm_cube, shared with the device's decision)
-        radius = std::min(o->max_trust_region_radius, radius);
+        if (dogleg) dl_step_accepted(it.relative_decrease, dl_step_norm, &radius, &mu);
+        else {
+          radius = radius / std::max(1.0 / 3.0, 1.0 - lm_cube(2.0 * it.relative_decrease - 1.0));   // ([EXT] pow(2 rho - 1, 3): lm_decide.h lm_cube, shared with the device's decision)
+          radius = std::min(o->max_trust_region_radius, radius);
+        }
         decrease_factor = 2.0;
         it.step_is_successful = 1;
         // the next step is computed right away so that one synchronisation per iteration suffices; when this was the last iteration the
@@ -142,10 +154,11 @@ struct LmState {
         return;
       }
       it.step_is_successful = 0;
-      radius = radius / decrease_factor; decrease_factor *= 2.0;
+      if (dogleg) dl_step_rejected(&radius);
+      else { radius = radius / decrease_factor; decrease_factor *= 2.0; }
       it.cost = cand_cost + fixed;
       if (last_iteration) continue;
-      request(STEP_REJECT, false);
+      request(dogleg ? STEP_REUSE : STEP_REJECT, false);
       return;
     }
     sum->final_cost = x_cost + fixed;

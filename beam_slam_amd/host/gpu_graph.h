@@ -24,8 +24,12 @@ extern "C" int bsgpu_covariance_requests(bsgpu_ctx* ctx, int32_t n_requests, con
 
 namespace ceres_compat {  // the ceres::Solver fields the reference sets (vio.yaml:7-17) and reads (fixed_lag_smoother.cpp:286,705-716)
 enum TerminationType { CONVERGENCE = 0, NO_CONVERGENCE = 1, FAILURE = 2 };
+enum TrustRegionStrategyType { LEVENBERG_MARQUARDT = 0, DOGLEG = 1 };
+enum DoglegType { TRADITIONAL_DOGLEG = 0, SUBSPACE_DOGLEG = 1 };
 struct SolverOptions {
   int max_num_iterations = 50;
+  TrustRegionStrategyType trust_region_strategy_type = LEVENBERG_MARQUARDT;   // (fuse_core::loadSolverOptionsFromROS reads both from solver_options:)
+  DoglegType dogleg_type = TRADITIONAL_DOGLEG;                                // SUBSPACE_DOGLEG: not implemented, optimize() throws
   double max_solver_time_in_seconds = 1e9;
   double function_tolerance = 1e-6, gradient_tolerance = 1e-10, parameter_tolerance = 1e-8;
   int num_threads = 1;                 // accepted and ignored: the device decides its own parallelism
@@ -581,8 +585,11 @@ class GpuGraph {
     bsgpu_options_default(&bo);
     bo.max_num_iterations = o.max_num_iterations; bo.max_solver_time_in_seconds = o.max_solver_time_in_seconds;
     bo.function_tolerance = o.function_tolerance; bo.gradient_tolerance = o.gradient_tolerance; bo.parameter_tolerance = o.parameter_tolerance;
+    bo.trust_region_strategy_type = o.trust_region_strategy_type == ceres_compat::LEVENBERG_MARQUARDT ? BSGPU_TR_LEVENBERG_MARQUARDT
+                                  : o.dogleg_type == ceres_compat::TRADITIONAL_DOGLEG ? BSGPU_TR_DOGLEG : BSGPU_TR_SUBSPACE_DOGLEG;
     bsgpu_summary bs;
     std::memset(&bs, 0, sizeof(bs));
+    if (bo.trust_region_strategy_type == BSGPU_TR_SUBSPACE_DOGLEG) check(bsgpu_solve(ctx(), &bo, &bs));   // (refused: the back-end's message, thrown)
     const int rc = bsgpu_solve(ctx(), &bo, &bs);
     if (rc != BSGPU_OK) {
       // a back-end error is what Ceres reports as a FAILURE summary (the caller — FixedLagSmoother::optimizationLoop, fixed_lag_smoother.cpp:281-292 —

@@ -180,6 +180,16 @@ enum {
                                       inexact: pcg_tolerance / pcg_max_iterations)        */
 };
 
+/* ---- trust-region strategy (ceres::Solver::Options::trust_region_strategy_type)
+ * DOGLEG is Ceres' TRADITIONAL_DOGLEG.  It needs an exact linear solve: PCG and SCHUR_PCG are
+ * refused (BSGPU_ERR_INVALID), as are an AUTO that resolves to the PCG, inverse-depth factors and
+ * bsgpu_localize_frames (BSGPU_ERR_UNSUPPORTED).  SUBSPACE_DOGLEG is not implemented. ---------- */
+enum {
+  BSGPU_TR_LEVENBERG_MARQUARDT = 0,
+  BSGPU_TR_DOGLEG = 1,
+  BSGPU_TR_SUBSPACE_DOGLEG = 2   /* BSGPU_ERR_UNSUPPORTED */
+};
+
 /* ---- termination (ceres::TerminationType) ---------------------------------- */
 enum {
   BSGPU_CONVERGENCE = 0,
@@ -205,7 +215,7 @@ typedef struct bsgpu_options {
   double min_lm_diagonal;               /* 1e-6                                 */
   double max_lm_diagonal;               /* 1e32                                 */
   int32_t pcg_max_iterations;           /* BSGPU_LINEAR_PCG only                */
-  int32_t reserved0;
+  int32_t trust_region_strategy_type;   /* BSGPU_TR_*; default LEVENBERG_MARQUARDT */
   double pcg_tolerance;                 /* relative residual |r| / |b| at which an inner solve stops.  Default 1e-10: the reference's
                                            step on this path is the exact SPARSE_NORMAL_CHOLESKY one, and a default-option caller (the
                                            global mapper) gets a step that is equivalent to it (69 inner iterations per LM step on the
@@ -386,6 +396,10 @@ int bsgpu_reset_values(bsgpu_ctx* ctx);
 
 int bsgpu_num_iterations_recorded(const bsgpu_ctx* ctx);
 int bsgpu_get_iteration(const bsgpu_ctx* ctx, int32_t i, bsgpu_iteration* out);
+/* linear systems the last bsgpu_solve on `ctx` assembled and solved: every Gauss-Newton / LM
+ * attempt, each DOGLEG mu retry included; a DOGLEG step that reuses its Gauss-Newton step after a
+ * rejection does not count */
+int bsgpu_num_factorizations(const bsgpu_ctx* ctx);
 
 /* ---- evaluation (ceres::Problem::Evaluate) --------------------------------- */
 /* Evaluates at the current values with the robust-loss corrector applied.
