@@ -532,7 +532,9 @@ int bsgpu_evaluate(bsgpu_ctx* c, double* cost, double* residuals, double* gradie
           if (cols[sl] < 0) continue;
           for (int j = 0; j < 3; ++j) {
             // stored: pose parts [n][A row 0 | A row 1] first, then the landmark parts [n][B row 0 | B row 1]
-            const double v = sl < 2 ? J[(size_t)i * kJAStride + 6 * k + 3 * sl + j] : J[(size_t)V.n * kJAStride + (size_t)i * 6 + 3 * k + j];
+            // (the compact layout — Visual::ja — keeps [theta row 0 | theta row 1] per factor: the t columns are the negated landmark part)
+            const double vb = J[(size_t)V.n * kJAStride + (size_t)i * 6 + 3 * k + j];
+            const double v = sl == 2 ? vb : V.ja == kJAStride ? J[(size_t)i * kJAStride + 6 * k + 3 * sl + j] : sl == 0 ? J[(size_t)i * kJACompact + 3 * k + j] : -vb;
             grad[cols[sl] + j] += v * r[2 * (size_t)i + k];
             if (jacobian) jacobian[(size_t)(row + k) * n + cols[sl] + j] = v;
           }
@@ -1194,7 +1196,7 @@ int64_t bsgpu_eval_bytes(const bsgpu_ctx* c) {
   static const struct { int idx, consts, res, jcols; } L[BSGPU_F_NUM_TYPES] = {
       {4, 3, 2, 9}, {6, 3, 2, 9}, {10, 287, 15, 30}, {5, 241, 15, 15}, {6, 43, 6, 12}, {4, 43, 6, 12}, {2, 43, 6, 6}, {1, 12, 3, 3},
       {2, 12, 3, 6}, {1, 7, 2, 3}, {6, 6, 2, 13}, {4, 6, 2, 7}, {10, 226, 15, 30}};
-  int64_t b = (int64_t)c->vis.n * 200 + (int64_t)c->h_x.size() * 8;
+  int64_t b = (int64_t)c->vis.n * (c->vis.ja == kJACompact ? 152 : 200) + (int64_t)c->h_x.size() * 8;   // (bsgpu_reproj_jacobian_bytes)
   for (int t = 2; t < BSGPU_F_NUM_TYPES && t < kNumInternal; ++t)
     b += (int64_t)c->small[t].n * (4 * L[t].idx + 8 * (L[t].consts + L[t].res + L[t].res * L[t].jcols));
   return b;
@@ -1215,9 +1217,9 @@ int bsgpu_profile_step(bsgpu_ctx* c, const bsgpu_options* o, int32_t reps, doubl
 } catch (...) { return api_exception(c); }
 int64_t bsgpu_reproj_jacobian_bytes(const bsgpu_ctx* c) {
   if (!c) return -1;
-  // per factor: 16 B (3 offsets + meta) + 16 B pixel + 8 B weight in, 16 B residual + 144 B Jacobian out;
-  // plus every parameter block once
-  return (int64_t)c->vis.n * 200 + (int64_t)c->h_x.size() * 8;
+  // per factor: 16 B (3 offsets + meta) + 16 B pixel + 8 B weight in, 16 B residual + 144 B Jacobian out (96 B with the compact pose part,
+  // Visual::ja); plus every parameter block once
+  return (int64_t)c->vis.n * (c->vis.ja == kJACompact ? 152 : 200) + (int64_t)c->h_x.size() * 8;
 }
 
 // Stand-alone dense SPD solve A x = b through the same plan + kernels the reduced camera system uses

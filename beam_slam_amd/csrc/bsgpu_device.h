@@ -11,6 +11,13 @@ namespace bsg {
 
 #define BSG_DEV __device__ __forceinline__
 
+// entry (row rw, pose column j: theta 0..2, t 3..5) of factor f's pose part of the reprojection Jacobian under either layout (Visual::ja; the
+// compact one keeps no t columns: they are the negated landmark part) — for the readers off the hot path
+BSG_DEV double pose_part_entry(const double* __restrict__ J, const double* __restrict__ JB, int ja, int f, int rw, int j) {
+  if (ja == kJAStride) return J[(size_t)f * kJAStride + 6 * rw + j];
+  return j < 3 ? J[(size_t)f * kJACompact + 3 * rw + j] : -JB[(size_t)f * 6 + 3 * rw + (j - 3)];
+}
+
 // Eigen::Quaternion::toRotationMatrix() (no normalisation) — what the reprojection factor uses
 // (euclidean_reprojection_function.h:68-70).  R row-major.
 BSG_DEV void quat_to_rot(const double q[4], double R[9]) {

@@ -514,6 +514,10 @@ int finalize(bsgpu_ctx* c) {
     // (bsgpu_internal.h Visual::no_cr: every factor belongs to a band landmark)
     const char* no_cr_env = getenv("BSGPU_NO_CR");
     V.no_cr = !(no_cr_env && atoi(no_cr_env) == 0) && V.n_band_units > 0 && V.n_seg == 0 && V.n_ent == 0 && V.n == V.n_elim && V.band_lm_id != nullptr && V.Linv && V.z;
+    // (Visual::ja: the windows without C rows keep no translation columns in the pose part either — no factor of a constant landmark, and every reader of
+    //  the layout has the B rows at hand.  J above stays sized for the full layout, JB in its place behind it: the choice needs the tables it is made from.)
+    const char* compact_env = getenv("BSGPU_COMPACT_J");
+    V.ja = V.no_cr && !(compact_env && atoi(compact_env) == 0) ? kJACompact : kJAStride;
   }
   lap("visual upload + alloc");
   // ---- pose-only groups

@@ -29,6 +29,10 @@ struct DevLoss {
 // row pitch (doubles) of the pose part of the reprojection Jacobian.  (Padding the rows to one 128-byte line each, pitch 16, was
 // tried for the pair kernel's gathers: no gain there, and the evaluation kernel's partial-line streaming stores went 18 -> 31 us.)
 constexpr int kJAStride = 12;
+// ... of the COMPACT layout (Visual::ja): the orientation columns only, [theta row 0 (3) | theta row 1 (3)].  The translation columns of the
+// pose part are d r / d t = M R^T and the landmark part is d r / d P = -M R^T: where the stored B row is that product (the landmark is not
+// constant) they are its exact negation and every reader forms them from the B row it reads anyway.
+constexpr int kJACompact = 6;
 
 // entries of one camera pair are cut into segments of at most this many (one single-wave workgroup of pairs_kernel each);
 // a power of two.  Host and device flattening must agree (their tables are compared bit for bit).
@@ -145,10 +149,15 @@ struct Visual {
   // entries, no factors of constant landmarks) the two consumers form C and rho themselves from the B rows (48 B, which they have or read instead)
   // and the landmark's Linv and z: lone solves pass CR = nullptr to the three launches; the batched launches keep the C rows.  BSGPU_NO_CR=0: never.
   bool no_cr = false;
+  // COMPACT POSE PART.  Pose-part pitch of J in doubles: kJAStride, or kJACompact when the window keeps no translation columns (48 B per factor less written
+  // by the evaluation and read by the band kernel and the back-substitution).  Chosen at finalize for the windows without C rows (no_cr: no factor
+  // of a constant landmark, so every stored B is the true -M R^T; a constant POSITION is skipped by every reader through cp_tp < 0, never through the
+  // stored zeros).  Every other window keeps the full layout and its code paths.  BSGPU_COMPACT_J=0: never.
+  int ja = kJAStride;
   // outputs
   double2* r = nullptr;       // n
-  double* J = nullptr;        // robustified Jacobian, split by consumer: pose part n x 12 ([A row 0 (theta, t: 6) | A row 1]) ...
-  double* JB = nullptr;       // ... and landmark part n x 6 ([B row 0 | B row 1]) = J + 12 n: the landmark kernel streams 48 B per factor
+  double* J = nullptr;        // robustified Jacobian, split by consumer: pose part n x ja ([A row 0 (theta, t: 6) | A row 1], compact: [theta row 0 | theta row 1]) ...
+  double* JB = nullptr;       // ... and landmark part n x 6 ([B row 0 | B row 1]) = J + 12 n (either layout): the landmark kernel streams 48 B per factor
                               // instead of dragging 144-byte rows through for a third of their bytes
   double* CR = nullptr;       // n x 8: C = B M (2x3), rho = r - C z (2)
   // per landmark ONE record of kLmRec doubles (80 B, 16-byte aligned): [Linv (6: lower-triangular inverse factor of Hll + lambda) | z = Linv g_l (3) | pad] — the

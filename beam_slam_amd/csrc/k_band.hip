@@ -39,6 +39,7 @@ static_assert((kBandPitch / 2) % 2 == 1 && 3 * kBandNL % 4 == 0 && 64 % kBandNL 
 // 16-byte pieces per landmark in the stage (A: 6 per observation, C | rho: 4, r: 1; odd strides: the 16-byte reads of the forming lanes,
 // one landmark each, fall on different banks)
 constexpr int kBandStA = 81, kBandStC = 65, kBandStR = 17;   // (>= 16 x 5, 16 x 4, 16: every loader thread stores every piece it requested, no conditions)
+constexpr int kBandStACompact = 49;   // (>= 16 x 3) the compact pose part (Visual::ja == kJACompact): 3 pieces per observation, three requests per loader thread
 constexpr size_t kBandLds = sizeof(double) * kBandRows * kBandPitch + sizeof(int) * kBandRows + 16 * (size_t)kBandNL * (kBandStA + kBandStC + kBandStR + 1);
 static_assert(kBandCams * 6 <= kBandRows && kBandCams <= 13, "slot nibbles, tile rows");
 static_assert(sizeof(double) * (15 * 30 + 16) + sizeof(int) * 16 <= kBandLds, "a riding pose-only factor's staging");
@@ -58,17 +59,19 @@ BSG_DEV int4 band_fetch_rec(const int4* __restrict__ band_lm, int li, int end) {
 // Plain named locals and unconditional loads at clamped indices: a struct handed to helpers is an object in memory across the barriers' asm
 // (it lived in scratch: 176 bytes per lane), and arrays of loaded values under a lane condition went to scratch in round 3's band kernel.
 // (NOCR — Visual::no_cr: the stage's C area takes the landmark's B rows, 3 pieces per observation, in pieces 0 .. 47, and the landmark's Linv (pieces
-//  48 .. 50) and z (pieces 51, 52: z0 z1 | z2 pad — the landmark's 80-byte record as it lies in memory) instead of the C | rho rows; LMID = the record's landmark)
+//  48 .. 50) and z (pieces 51, 52: z0 z1 | z2 pad — the landmark's 80-byte record as it lies in memory) instead of the C | rho rows; LMID = the record's landmark.
+//  COMPACT — only with NOCR: the A rows are [theta row 0 | theta row 1], 3 pieces per observation; the forming lane takes the translation columns from the B rows)
 #define BSG_BAND_ISSUE(REC, LMID)                                                                                             \
   {                                                                                                                           \
     const int n_ = (int)((unsigned)(REC).y >> 24);                                                                            \
     const int cpo_ = NOCR ? 3 : 4;                                                                                            \
-    const int na_ = 6 * n_ - 1 > 0 ? 6 * n_ - 1 : 0, nc_ = cpo_ * n_ - 1 > 0 ? cpo_ * n_ - 1 : 0, nr_ = n_ - 1 > 0 ? n_ - 1 : 0; \
-    const double2* Jf_ = J2 + (size_t)(REC).x * (kJAStride / 2);                                                              \
+    const int apo_ = COMPACT ? 3 : 6;                                                                                         \
+    const int na_ = apo_ * n_ - 1 > 0 ? apo_ * n_ - 1 : 0, nc_ = cpo_ * n_ - 1 > 0 ? cpo_ * n_ - 1 : 0, nr_ = n_ - 1 > 0 ? n_ - 1 : 0; \
+    const double2* Jf_ = J2 + (size_t)(REC).x * apo_;                                                                         \
     const double2* Cf_ = C2 + (size_t)(REC).x * cpo_;                                                                         \
     const double2* rf_ = r + (size_t)(REC).x;                                                                                 \
-    pa0 = Jf_[min(l16, na_)]; pa1 = Jf_[min(l16 + 16, na_)]; pa2 = Jf_[min(l16 + 32, na_)]; pa3 = Jf_[min(l16 + 48, na_)];     \
-    pa4 = Jf_[min(l16 + 64, na_)];                                                                                            \
+    pa0 = Jf_[min(l16, na_)]; pa1 = Jf_[min(l16 + 16, na_)]; pa2 = Jf_[min(l16 + 32, na_)];                                    \
+    if (!COMPACT) { pa3 = Jf_[min(l16 + 48, na_)]; pa4 = Jf_[min(l16 + 64, na_)]; }                                                                                      \
     pc0 = Cf_[min(l16, nc_)]; pc1 = Cf_[min(l16 + 16, nc_)]; pc2 = Cf_[min(l16 + 32, nc_)];                                    \
     if (NOCR) pc3 = reinterpret_cast<const double2*>(Linv + (size_t)(LMID) * kLmRec)[min(l16, 4)];   /* the landmark's record: Linv | z | pad */ \
     else pc3 = Cf_[min(l16 + 48, nc_)];                                                                                       \
@@ -77,8 +80,9 @@ BSG_DEV int4 band_fetch_rec(const int4* __restrict__ band_lm, int li, int end) {
   }
 #define BSG_BAND_STAGE()                                                                                                      \
   {                                                                                                                           \
-    double2* a_ = sA + g * kBandStA; double2* c_ = sC + g * kBandStC; double2* rr_ = sR + g * kBandStR;                        \
-    a_[l16] = pa0; a_[l16 + 16] = pa1; a_[l16 + 32] = pa2; a_[l16 + 48] = pa3; a_[l16 + 64] = pa4;                             \
+    double2* a_ = sA + g * kStA;     double2* c_ = sC + g * kBandStC; double2* rr_ = sR + g * kBandStR;                        \
+    a_[l16] = pa0; a_[l16 + 16] = pa1; a_[l16 + 32] = pa2;                                                                  \
+    if (!COMPACT) { a_[l16 + 48] = pa3; a_[l16 + 64] = pa4; }                                                                 \
     c_[l16] = pc0; c_[l16 + 16] = pc1; c_[l16 + 32] = pc2; c_[l16 + 48] = pc3;                                                 \
     rr_[l16] = pr0;                                                                                                           \
     if (l16 == 0) sRec[g] = prec;                                                                                             \
@@ -122,8 +126,10 @@ BSG_DEV void band_multiply(const unsigned (&za)[kBandNT], const unsigned (&zb)[k
 }
 
 // NOCR: CR = the landmark parts of the Jacobian rows (Visual::JB, 48 B per observation), lm_id / Linv / z = the records' landmarks and their inverse factors
-template <bool NOCR = false>
+template <bool NOCR = false, bool COMPACT = false>
 __device__ __forceinline__ void pairs_band_kernel_body(const int bsg_bx, const int bsg_gx, int n_units, const int* __restrict__ unit_start, const int* __restrict__ unit_cam, const int4* __restrict__ band_lm, int n_cam_pose, const double* __restrict__ J, const double2* __restrict__ r, const double* __restrict__ CR, const int* __restrict__ cp_tq, const int* __restrict__ cp_tp, double* __restrict__ S, int ld, int rhs_row, double* __restrict__ grad, double* __restrict__ hdiag, const int* __restrict__ perm, int grad_only, const SmallGroupSet& small, int n_small_units, const int* __restrict__ lm_id = nullptr, const double* __restrict__ Linv = nullptr, const double* __restrict__ z = nullptr) {
+  static_assert(NOCR || !COMPACT, "the compact pose part needs the B rows in the stage");
+  constexpr int kStA = COMPACT ? kBandStACompact : kBandStA;   // (the stage's areas keep their places: the A area is sized for the full layout)
   extern __shared__ __attribute__((aligned(16))) double bsm[];
   const int tid = threadIdx.x;
   const int u = bsg_bx;
@@ -213,13 +219,14 @@ __device__ __forceinline__ void pairs_band_kernel_body(const int bsg_bx, const i
       // (unconditional reads at a clamped observation, then a select: loads under a lane condition into array elements go to scratch memory;
       //  the stage may hold anything where no row was written — a product with zero would not do)
       const int oc = valid ? oi : 0;
-      const double2* a = sA + lmk * kBandStA + 6 * oc;
+      const double2* a = sA + lmk * kStA + (COMPACT ? 3 : 6) * oc;
       const double2* c = sC + lmk * kBandStC + (NOCR ? 3 : 4) * oc;
-      const double2 a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], a4 = a[4], a5 = a[5], c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[NOCR ? 2 : 3];
+      const double2 a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[COMPACT ? 0 : 3], a4 = a[COMPACT ? 0 : 4], a5 = a[COMPACT ? 0 : 5], c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[NOCR ? 2 : 3];
       const double2 rr = sR[lmk * kBandStR + oc];
 #define BSG_SEL(x) (valid ? (x) : 0.0)
-      const double A0[6] = {BSG_SEL(a0.x), BSG_SEL(a0.y), BSG_SEL(a1.x), BSG_SEL(a1.y), BSG_SEL(a2.x), BSG_SEL(a2.y)};
-      const double A1[6] = {BSG_SEL(a3.x), BSG_SEL(a3.y), BSG_SEL(a4.x), BSG_SEL(a4.y), BSG_SEL(a5.x), BSG_SEL(a5.y)};
+      // (COMPACT: [theta row 0 | theta row 1] in three pieces; the translation columns are the negated, unscaled B rows — exactly what the full layout stores)
+      const double A0[6] = {BSG_SEL(a0.x), BSG_SEL(a0.y), BSG_SEL(a1.x), BSG_SEL(COMPACT ? -c0.x : a1.y), BSG_SEL(COMPACT ? -c0.y : a2.x), BSG_SEL(COMPACT ? -c1.x : a2.y)};
+      const double A1[6] = {BSG_SEL(COMPACT ? a1.y : a3.x), BSG_SEL(COMPACT ? a2.x : a3.y), BSG_SEL(COMPACT ? a2.y : a4.x), BSG_SEL(COMPACT ? -c1.y : a4.y), BSG_SEL(COMPACT ? -c2.x : a5.x), BSG_SEL(COMPACT ? -c2.y : a5.y)};
       double Ca[3] = {BSG_SEL(c0.x), BSG_SEL(c0.y), BSG_SEL(c1.x)}, Cb[3] = {BSG_SEL(c1.y), BSG_SEL(c2.x), BSG_SEL(c2.y)};
       const double r0 = BSG_SEL(rr.x), r1 = BSG_SEL(rr.y);
       double p0 = BSG_SEL(c3.x), p1 = BSG_SEL(c3.y);
@@ -351,10 +358,12 @@ __global__ __launch_bounds__(kBandThreads) void pairs_band_kernel(int n_units, c
   if (go.p && !(__hip_atomic_load(go.p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0.0)) return;   // (an assembly ahead whose step was not accepted)
   pairs_band_kernel_body((int)blockIdx.x, (int)gridDim.x, n_units, unit_start, unit_cam, band_lm, n_cam_pose, J, r, CR, cp_tq, cp_tp, S, ld, rhs_row, grad, hdiag, perm, grad_only, small, n_small_units);
 }
-// ... without C rows (Visual::no_cr): the landmark parts of the Jacobian rows instead, and the landmarks' Linv and z
+// ... without C rows (Visual::no_cr): the landmark parts of the Jacobian rows instead, and the landmarks' Linv and z; COMPACT: the pose part without
+// its translation columns (Visual::ja == kJACompact)
+template <bool COMPACT>
 __global__ __launch_bounds__(kBandThreads) void pairs_band_nocr_kernel(int n_units, const int* __restrict__ unit_start, const int* __restrict__ unit_cam, const int4* __restrict__ band_lm, int n_cam_pose, const double* __restrict__ J, const double2* __restrict__ r, const double* __restrict__ JB, const int* __restrict__ cp_tq, const int* __restrict__ cp_tp, double* __restrict__ S, int ld, int rhs_row, double* __restrict__ grad, double* __restrict__ hdiag, const int* __restrict__ perm, int grad_only, SmallGroupSet small, int n_small_units, const int* __restrict__ lm_id, const double* __restrict__ Linv, const double* __restrict__ z, GoWord go) {
   if (go.p && !(__hip_atomic_load(go.p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > 0.0)) return;
-  pairs_band_kernel_body<true>((int)blockIdx.x, (int)gridDim.x, n_units, unit_start, unit_cam, band_lm, n_cam_pose, J, r, JB, cp_tq, cp_tp, S, ld, rhs_row, grad, hdiag, perm, grad_only, small, n_small_units, lm_id, Linv, z);
+  pairs_band_kernel_body<true, COMPACT>((int)blockIdx.x, (int)gridDim.x, n_units, unit_start, unit_cam, band_lm, n_cam_pose, J, r, JB, cp_tq, cp_tp, S, ld, rhs_row, grad, hdiag, perm, grad_only, small, n_small_units, lm_id, Linv, z);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
 struct pairs_band_kernel_Args {
@@ -383,6 +392,7 @@ struct pairs_band_kernel_Args {
   const int* lm_id;
   const double* Linv;
   const double* z;
+  int ja;   // (Visual::ja: the pitch of J's pose part)
 };
 // (the same entry as the kernel reads it: its pointers are GLOBAL pointers — read as generic ones every load through them would be a FLAT
 // instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic)
@@ -411,6 +421,7 @@ struct pairs_band_kernel_ArgsG {
   const int __attribute__((address_space(1)))* lm_id;
   const double __attribute__((address_space(1)))* Linv;
   const double __attribute__((address_space(1)))* z;
+  int ja;
 };
 static_assert(sizeof(pairs_band_kernel_ArgsG) == sizeof(pairs_band_kernel_Args), "layout");
 
@@ -422,7 +433,9 @@ __global__ __launch_bounds__(kBandThreads) void pairs_band_kernel_batch(const pa
   //  a window's gradient-only step adds no tiles at all)
   const int band_mode = bsg_dyn->grad_only[bsg_w] ? 1 : 2;
   // (a window without C rows — Visual::no_cr — forms them from B, Linv and z as its lone launch does)
-  if (a.Linv)
+  if (a.Linv && a.ja == kJACompact)
+    pairs_band_kernel_body<true, true>((int)blockIdx.x, a.bsg_grid, a.n_units, (const int*)a.unit_start, (const int*)a.unit_cam, (const int4*)a.band_lm, a.n_cam_pose, (const double*)a.J, (const double2*)a.r, (const double*)a.JB, (const int*)a.cp_tq, (const int*)a.cp_tp, (double*)a.S, a.ld, a.rhs_row, (double*)a.grad, (double*)a.hdiag, (const int*)a.perm, band_mode, a.small, a.n_small_units, (const int*)a.lm_id, (const double*)a.Linv, (const double*)a.z);
+  else if (a.Linv)
     pairs_band_kernel_body<true>((int)blockIdx.x, a.bsg_grid, a.n_units, (const int*)a.unit_start, (const int*)a.unit_cam, (const int4*)a.band_lm, a.n_cam_pose, (const double*)a.J, (const double2*)a.r, (const double*)a.JB, (const int*)a.cp_tq, (const int*)a.cp_tp, (double*)a.S, a.ld, a.rhs_row, (double*)a.grad, (double*)a.hdiag, (const int*)a.perm, band_mode, a.small, a.n_small_units, (const int*)a.lm_id, (const double*)a.Linv, (const double*)a.z);
   else
   pairs_band_kernel_body((int)blockIdx.x, a.bsg_grid, a.n_units, (const int*)a.unit_start, (const int*)a.unit_cam, (const int4*)a.band_lm, a.n_cam_pose, (const double*)a.J, (const double2*)a.r, (const double*)a.CR, (const int*)a.cp_tq, (const int*)a.cp_tp, (double*)a.S, a.ld, a.rhs_row, (double*)a.grad, (double*)a.hdiag, (const int*)a.perm, band_mode, a.small, a.n_small_units);
@@ -441,7 +454,8 @@ static int band_attr_state(int dev) {   // 1: available, -1: not
     bool ok = hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && max_lds >= (int)kBandLds;
     ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(pairs_band_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBandLds) == hipSuccess;
     ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(pairs_band_kernel_batch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBandLds) == hipSuccess;
-    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(pairs_band_nocr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBandLds) == hipSuccess;
+    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(pairs_band_nocr_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBandLds) == hipSuccess;
+    ok = ok && hipFuncSetAttribute(reinterpret_cast<const void*>(pairs_band_nocr_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBandLds) == hipSuccess;
     if (!ok) { (void)hipGetLastError(); fprintf(stderr, "[bsgpu] device %d gives %d B of LDS per workgroup, the band kernel needs %d: pair-entry path\n", dev, max_lds, (int)kBandLds); }
     state[dev] = ok ? 1 : -1;
   }
@@ -461,8 +475,12 @@ void launch_pairs_band(hipStream_t s, const Visual& v, double* S, int ld, int rh
   SmallGroupSet none;
   none.n = 0;
   const int riders = small ? n_small_units : 0;
-  if (v.no_cr)
-    hipLaunchKernelGGL(pairs_band_nocr_kernel, dim3(riders + v.n_band_units), dim3(kBandThreads), kBandLds, s, v.n_band_units, v.band_unit_start, v.band_unit_cam, v.band_lm,
+  if (v.no_cr && v.ja == kJACompact)
+    hipLaunchKernelGGL(pairs_band_nocr_kernel<true>, dim3(riders + v.n_band_units), dim3(kBandThreads), kBandLds, s, v.n_band_units, v.band_unit_start, v.band_unit_cam, v.band_lm,
+                       v.n_cam_pose, v.J, v.r, v.JB, v.cp_tq, v.cp_tp, S, ld, rhs_row, grad, hdiag, perm, (grad_only ? 1 : 0) | (lower_only ? 2 : 0), small ? *small : none, riders, v.band_lm_id,
+                       v.Linv, v.z, go);
+  else if (v.no_cr)
+    hipLaunchKernelGGL(pairs_band_nocr_kernel<false>, dim3(riders + v.n_band_units), dim3(kBandThreads), kBandLds, s, v.n_band_units, v.band_unit_start, v.band_unit_cam, v.band_lm,
                        v.n_cam_pose, v.J, v.r, v.JB, v.cp_tq, v.cp_tp, S, ld, rhs_row, grad, hdiag, perm, (grad_only ? 1 : 0) | (lower_only ? 2 : 0), small ? *small : none, riders, v.band_lm_id,
                        v.Linv, v.z, go);
   else
@@ -479,7 +497,7 @@ void batchargs_pairs_band(BatchArgTable& t, const Visual& v, double* S, int ld, 
   a.n_units = v.n_band_units; a.unit_start = v.band_unit_start; a.unit_cam = v.band_unit_cam; a.band_lm = v.band_lm; a.n_cam_pose = v.n_cam_pose;
   a.J = v.J; a.r = v.r; a.CR = v.CR; a.cp_tq = v.cp_tq; a.cp_tp = v.cp_tp; a.S = S; a.ld = ld; a.rhs_row = rhs_row; a.grad = grad; a.hdiag = hdiag; a.perm = perm;
   a.grad_only = 0; a.small = small ? *small : none; a.n_small_units = riders;
-  a.JB = v.no_cr ? v.JB : nullptr; a.lm_id = v.no_cr ? v.band_lm_id : nullptr; a.Linv = v.no_cr ? v.Linv : nullptr; a.z = v.no_cr ? v.z : nullptr;
+  a.JB = v.no_cr ? v.JB : nullptr; a.lm_id = v.no_cr ? v.band_lm_id : nullptr; a.Linv = v.no_cr ? v.Linv : nullptr; a.z = v.no_cr ? v.z : nullptr; a.ja = v.ja;
   t.push(a);
 }
 void launch_pairs_band_batch(hipStream_t s, const BatchArgTable& t, const BatchDyn* dyn, int list, int n) {

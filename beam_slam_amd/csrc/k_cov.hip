@@ -15,7 +15,7 @@
 namespace bsg {
 
 __global__ __launch_bounds__(64) void cov_rows_kernel(double* __restrict__ S, int ld, int rhs_row, const CovRow* __restrict__ rows,
-                                                      const int* __restrict__ dpos, const int* __restrict__ lm_start, const double* __restrict__ J,
+                                                      const int* __restrict__ dpos, const int* __restrict__ lm_start, const double* __restrict__ J, int ja,
                                                       const double* __restrict__ JB, const int* __restrict__ cam_pose, const int* __restrict__ cp_tq,
                                                       const int* __restrict__ cp_tp, const double* __restrict__ Linv, const int* __restrict__ view_start,
                                                       const int* __restrict__ view_cp, const int* __restrict__ icp_tq, const int* __restrict__ icp_tp,
@@ -56,18 +56,17 @@ __global__ __launch_bounds__(64) void cov_rows_kernel(double* __restrict__ S, in
     const int tb = j < 3 ? cp_tq[cp] : cp_tp[cp];
     if (tb < 0) continue;
     const double* B = JB + (size_t)f * 6;        // [B row 0 | B row 1]
-    const double* A = J + (size_t)f * kJAStride;  // [A row 0 (theta, t) | A row 1]
     const double s0 = vi[0] * B[0] + vi[1] * B[1] + vi[2] * B[2];
     const double s1 = vi[0] * B[3] + vi[1] * B[4] + vi[2] * B[5];
     double* o = out + dpos[tb + (j % 3)];
-    *o += s0 * A[j] + s1 * A[6 + j];
+    *o += s0 * pose_part_entry(J, JB, ja, f, 0, j) + s1 * pose_part_entry(J, JB, ja, f, 1, j);
   }
 }
 
 void launch_cov_rows(hipStream_t s, double* S, int ld, int rhs_row, const CovRow* rows, int n_rows, const int* dpos, const Visual& v, const IdpElim& e) {
   (void)hipMemsetAsync(S + (size_t)rhs_row * ld, 0, sizeof(double) * 64 * (size_t)ld, s);
   if (n_rows <= 0) return;
-  hipLaunchKernelGGL(cov_rows_kernel, dim3(n_rows), dim3(64), 0, s, S, ld, rhs_row, rows, dpos, v.lm_start, v.J, v.JB, v.cam_pose, v.cp_tq, v.cp_tp,
+  hipLaunchKernelGGL(cov_rows_kernel, dim3(n_rows), dim3(64), 0, s, S, ld, rhs_row, rows, dpos, v.lm_start, v.J, v.ja, v.JB, v.cam_pose, v.cp_tq, v.cp_tp,
                      v.Linv, e.view_start, e.view_cp, e.cp_tq, e.cp_tp, e.U, e.linv);
 }
 

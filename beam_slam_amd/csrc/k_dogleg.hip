@@ -54,19 +54,18 @@ __global__ __launch_bounds__(kDlThreads) void dl_step_kernel(int n_tan, const do
 
 // reprojection factors: 8 lanes per eliminated landmark (its factors are contiguous, lm_start), then one lane per factor of a constant landmark
 __global__ __launch_bounds__(kDlThreads) void dl_jv_vis_kernel(int n_lm, int n_lm_groups, int n_elim, int n, int n_pose, const int* __restrict__ lm_start,
-                                                               const double* __restrict__ J, const double* __restrict__ JB, const double2* __restrict__ r,
+                                                               const double* __restrict__ J, int ja, const double* __restrict__ JB, const double2* __restrict__ r,
                                                                const int* __restrict__ cam_pose, const int* __restrict__ cp_tq, const int* __restrict__ cp_tp,
                                                                const double* __restrict__ u, double* __restrict__ part) {
   __shared__ double sred[4];
   double jj = 0.0, jr = 0.0;
   auto factor = [&](int f, const double* ul) {
-    const double* A = J + (size_t)f * kJAStride;
     const int cp = cam_pose[f], tq = cp_tq[cp], tp = cp_tp[cp];
     double j0 = 0.0, j1 = 0.0;
     if (tq >= 0)
-      for (int k = 0; k < 3; ++k) { const double uv = u[tq + k]; j0 += A[k] * uv; j1 += A[6 + k] * uv; }
+      for (int k = 0; k < 3; ++k) { const double uv = u[tq + k]; j0 += pose_part_entry(J, JB, ja, f, 0, k) * uv; j1 += pose_part_entry(J, JB, ja, f, 1, k) * uv; }
     if (tp >= 0)
-      for (int k = 0; k < 3; ++k) { const double uv = u[tp + k]; j0 += A[3 + k] * uv; j1 += A[9 + k] * uv; }
+      for (int k = 0; k < 3; ++k) { const double uv = u[tp + k]; j0 += pose_part_entry(J, JB, ja, f, 0, 3 + k) * uv; j1 += pose_part_entry(J, JB, ja, f, 1, 3 + k) * uv; }
     if (ul) {
       const double* B = JB + (size_t)f * 6;
       j0 += B[0] * ul[0] + B[1] * ul[1] + B[2] * ul[2];
@@ -173,7 +172,7 @@ void launch_dl_jv(hipStream_t s, const Visual& vis, int n_pose, const SmallGroup
     const int g_lm = (vis.n_lm * 8 + kDlThreads - 1) / kDlThreads, g_const = (vis.n - vis.n_elim + kDlThreads - 1) / kDlThreads;
     if (g_lm + g_const > 0)
       hipLaunchKernelGGL(dl_jv_vis_kernel, dim3(g_lm + g_const), dim3(kDlThreads), 0, s, vis.n_lm, g_lm, vis.n_elim, vis.n, n_pose, vis.lm_start, vis.J,
-                         vis.JB, vis.r, vis.cam_pose, vis.cp_tq, vis.cp_tp, u, part + 2 * (size_t)off);
+                         vis.ja, vis.JB, vis.r, vis.cam_pose, vis.cp_tq, vis.cp_tp, u, part + 2 * (size_t)off);
     off += g_lm + g_const;
   }
   for (int i = 0; i < n_small; ++i) {

@@ -20,10 +20,10 @@ __global__ __launch_bounds__(256) void reproj_eval_kernel(int n, const int4* __r
                                                           const double* __restrict__ wgt, const double* __restrict__ x,
                                                           const DevCamera* __restrict__ cams,
                                                           const DevLoss* __restrict__ losses,
-                                                          double2* __restrict__ r_out, double* __restrict__ J_out,
+                                                          double2* __restrict__ r_out, double* __restrict__ J_out, int ja,
                                                           double* __restrict__ JB_out, double* __restrict__ cost_part, int count_inactive) {
   __shared__ __attribute__((aligned(16))) double sJ[kReprojStage<WITH_J>];
-  reproj_eval_body<WITH_J>((int)blockIdx.x, n, fac, pix, wgt, x, cams, losses, r_out, J_out, JB_out, cost_part, count_inactive, sJ);
+  reproj_eval_body<WITH_J>((int)blockIdx.x, n, fac, pix, wgt, x, cams, losses, r_out, J_out, ja, JB_out, cost_part, count_inactive, sJ);
 }
 
 void launch_reproj_eval(hipStream_t s, const Visual& v, const double* x, const DevCamera* cams,
@@ -32,10 +32,10 @@ void launch_reproj_eval(hipStream_t s, const Visual& v, const double* x, const D
   const int grid = (v.n + 255) / 256;
   if (with_J)
     hipLaunchKernelGGL(reproj_eval_kernel<true>, dim3(grid), dim3(256), 0, s, v.n, v.fac, v.pix, v.w, x, cams, losses,
-                       v.r, v.J, v.JB, cost_part_out, count_inactive ? 1 : 0);
+                       v.r, v.J, v.ja, v.JB, cost_part_out, count_inactive ? 1 : 0);
   else
     hipLaunchKernelGGL(reproj_eval_kernel<false>, dim3(grid), dim3(256), 0, s, v.n, v.fac, v.pix, v.w, x, cams, losses,
-                       v.r, v.J, v.JB, cost_part_out, count_inactive ? 1 : 0);
+                       v.r, v.J, v.ja, v.JB, cost_part_out, count_inactive ? 1 : 0);
 }
 void launch_reproj_jacobian_only(hipStream_t s, const Visual& v, const double* x, const DevCamera* cams,
                                  const DevLoss* losses) {
@@ -587,7 +587,23 @@ BSG_DEV void pose_part(const double* __restrict__ Jf_row, int tq, int tp, const 
     for (int k = 0; k < 3; ++k) { const double yv = y_pose[tp + k]; j0 += Jf[3 + k] * yv; j1 += Jf[9 + k] * yv; }
   }
 }
-__device__ __forceinline__ void backsub_mcc_kernel_body(const int bsg_bx, const int bsg_gx, int n_lm, int n_lm_groups, int n_elim, int n, const int* __restrict__ lm_start, const double* __restrict__ J, const double* __restrict__ JB, const double2* __restrict__ r, const double* __restrict__ CR, const int* __restrict__ cam_pose, const int* __restrict__ cp_tq, const int* __restrict__ cp_tp, const double* __restrict__ Linv, const double* __restrict__ z, int n_pose, const double* __restrict__ y_pose, double* __restrict__ delta, double* __restrict__ mcc_part, int n_vis_blocks, const SmallGroupSet& small, int n_small_units, const UpdateRide& up, int first_update_block) {
+// ... of the compact layout (Visual::ja == kJACompact): the row holds [theta row 0 | theta row 1], the translation columns are the negated
+// landmark part B of the same factor, which every caller has loaded (-b y adds with the bits of t y: negation is exact)
+BSG_DEV void pose_part_compact(const double* __restrict__ Jf_row, const double (&B)[6], int tq, int tp, const double* __restrict__ y_pose, double& j0, double& j1) {
+  const double2* J2 = reinterpret_cast<const double2*>(Jf_row);
+  const double2 v0 = J2[0], v1 = J2[1], v2 = J2[2];
+  const double Jf[6] = {v0.x, v0.y, v1.x, v1.y, v2.x, v2.y};
+  j0 = 0.0; j1 = 0.0;
+  if (tq >= 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { const double yv = y_pose[tq + k]; j0 += Jf[k] * yv; j1 += Jf[3 + k] * yv; }
+  }
+  if (tp >= 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { const double yv = y_pose[tp + k]; j0 += (-B[k]) * yv; j1 += (-B[3 + k]) * yv; }
+  }
+}
+__device__ __forceinline__ void backsub_mcc_kernel_body(const int bsg_bx, const int bsg_gx, int n_lm, int n_lm_groups, int n_elim, int n, const int* __restrict__ lm_start, const double* __restrict__ J, int ja, const double* __restrict__ JB, const double2* __restrict__ r, const double* __restrict__ CR, const int* __restrict__ cam_pose, const int* __restrict__ cp_tq, const int* __restrict__ cp_tp, const double* __restrict__ Linv, const double* __restrict__ z, int n_pose, const double* __restrict__ y_pose, double* __restrict__ delta, double* __restrict__ mcc_part, int n_vis_blocks, const SmallGroupSet& small, int n_small_units, const UpdateRide& up, int first_update_block) {
   __shared__ double sred[4];
   if (up.n_blocks > 0 && bsg_bx >= first_update_block) {
     // the candidate of every block but the Euclidean landmarks (those: below, by the lanes that compute their step): the pose step is
@@ -627,13 +643,15 @@ __device__ __forceinline__ void backsub_mcc_kernel_body(const int bsg_bx, const 
     int it = 0;
     // (no C rows — Visual::no_cr: the sums are taken with the B rows, sum_a B_a^T (A_a y), and C^T = Linv B^T is applied to them once per landmark below)
     const bool no_cr = CR == nullptr;
+    const bool compact = ja == kJACompact;
     for (int f = beg + sub; f < end; f += 8, ++it) {
       const double2* C2 = no_cr ? reinterpret_cast<const double2*>(JB + (size_t)f * 6) : reinterpret_cast<const double2*>(CR + (size_t)f * 8);
       const double2 ca = C2[0], cb = C2[1], cc = C2[2];
       const double C[6] = {ca.x, ca.y, cb.x, cb.y, cc.x, cc.y};
       const int cp = cam_pose[f];
       double j0, j1;
-      pose_part(J + (size_t)f * kJAStride, cp_tq[cp], cp_tp[cp], y_pose, j0, j1);
+      if (compact) pose_part_compact(J + (size_t)f * kJACompact, C, cp_tq[cp], cp_tp[cp], y_pose, j0, j1);   // (compact implies no C rows: C is the B row)
+      else pose_part(J + (size_t)f * kJAStride, cp_tq[cp], cp_tp[cp], y_pose, j0, j1);
       if (it == 0) { jk0[0] = j0; jk1[0] = j1; } else if (it == 1) { jk0[1] = j0; jk1[1] = j1; }
       a0 += C[0] * j0 + C[3] * j1; a1 += C[1] * j0 + C[4] * j1; a2 += C[2] * j0 + C[5] * j1;
     }
@@ -669,6 +687,7 @@ __device__ __forceinline__ void backsub_mcc_kernel_body(const int bsg_bx, const 
         double j0, j1;
         if (it == 0) { j0 = jk0[0]; j1 = jk1[0]; }
         else if (it == 1) { j0 = jk0[1]; j1 = jk1[1]; }
+        else if (compact) { const int cp = cam_pose[f]; pose_part_compact(J + (size_t)f * kJACompact, Bf, cp_tq[cp], cp_tp[cp], y_pose, j0, j1); }
         else { const int cp = cam_pose[f]; pose_part(J + (size_t)f * kJAStride, cp_tq[cp], cp_tp[cp], y_pose, j0, j1); }
         const double d0 = -(j0 + Bf[0] * y0 + Bf[1] * y1 + Bf[2] * y2), d1 = -(j1 + Bf[3] * y0 + Bf[4] * y1 + Bf[5] * y2);
         const double2 rf = r[f];
@@ -680,7 +699,7 @@ __device__ __forceinline__ void backsub_mcc_kernel_body(const int bsg_bx, const 
     if (f < n) {
       const int cp = cam_pose[f];
       double j0, j1;
-      pose_part(J + (size_t)f * kJAStride, cp_tq[cp], cp_tp[cp], y_pose, j0, j1);
+      pose_part(J + (size_t)f * kJAStride, cp_tq[cp], cp_tp[cp], y_pose, j0, j1);   // (a window with factors of constant landmarks keeps the full layout)
       const double2 rf = r[f];
       acc = -((-j0) * (rf.x - 0.5 * j0) + (-j1) * (rf.y - 0.5 * j1));
     }
@@ -694,8 +713,8 @@ __device__ __forceinline__ void backsub_mcc_kernel_body(const int bsg_bx, const 
     if (threadIdx.x == 0) { up.part[2 * slot] = a; up.part[2 * slot + 1] = c; }
   }
 }
-__global__ __launch_bounds__(256) void backsub_mcc_kernel(int n_lm, int n_lm_groups, int n_elim, int n, const int* __restrict__ lm_start, const double* __restrict__ J, const double* __restrict__ JB, const double2* __restrict__ r, const double* __restrict__ CR, const int* __restrict__ cam_pose, const int* __restrict__ cp_tq, const int* __restrict__ cp_tp, const double* __restrict__ Linv, const double* __restrict__ z, int n_pose, const double* __restrict__ y_pose, double* __restrict__ delta, double* __restrict__ mcc_part, int n_vis_blocks, SmallGroupSet small, int n_small_units, UpdateRide up, int first_update_block) {
-  backsub_mcc_kernel_body((int)blockIdx.x, (int)gridDim.x, n_lm, n_lm_groups, n_elim, n, lm_start, J, JB, r, CR, cam_pose, cp_tq, cp_tp, Linv, z, n_pose, y_pose, delta, mcc_part, n_vis_blocks, small, n_small_units, up, first_update_block);
+__global__ __launch_bounds__(256) void backsub_mcc_kernel(int n_lm, int n_lm_groups, int n_elim, int n, const int* __restrict__ lm_start, const double* __restrict__ J, int ja, const double* __restrict__ JB, const double2* __restrict__ r, const double* __restrict__ CR, const int* __restrict__ cam_pose, const int* __restrict__ cp_tq, const int* __restrict__ cp_tp, const double* __restrict__ Linv, const double* __restrict__ z, int n_pose, const double* __restrict__ y_pose, double* __restrict__ delta, double* __restrict__ mcc_part, int n_vis_blocks, SmallGroupSet small, int n_small_units, UpdateRide up, int first_update_block) {
+  backsub_mcc_kernel_body((int)blockIdx.x, (int)gridDim.x, n_lm, n_lm_groups, n_elim, n, lm_start, J, ja, JB, r, CR, cam_pose, cp_tq, cp_tp, Linv, z, n_pose, y_pose, delta, mcc_part, n_vis_blocks, small, n_small_units, up, first_update_block);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
 struct backsub_mcc_kernel_Args {
@@ -706,6 +725,7 @@ struct backsub_mcc_kernel_Args {
   int n;
   const int* lm_start;
   const double* J;
+  int ja;
   const double* JB;
   const double2* r;
   const double* CR;
@@ -734,6 +754,7 @@ struct backsub_mcc_kernel_ArgsG {
   int n;
   const int __attribute__((address_space(1)))* lm_start;
   const double __attribute__((address_space(1)))* J;
+  int ja;
   const double __attribute__((address_space(1)))* JB;
   const double2 __attribute__((address_space(1)))* r;
   const double __attribute__((address_space(1)))* CR;
@@ -758,7 +779,7 @@ __global__ __launch_bounds__(256) void backsub_mcc_kernel_batch(const backsub_mc
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.y];
   const backsub_mcc_kernel_ArgsG& a = reinterpret_cast<const backsub_mcc_kernel_ArgsG*>(bsg_A)[bsg_w];
   if ((int)blockIdx.x >= a.bsg_grid) return;
-  backsub_mcc_kernel_body((int)blockIdx.x, a.bsg_grid, a.n_lm, a.n_lm_groups, a.n_elim, a.n, (const int*)a.lm_start, (const double*)a.J, (const double*)a.JB, (const double2*)a.r, (double*)a.CR, (const int*)a.cam_pose, (const int*)a.cp_tq, (const int*)a.cp_tp, (const double*)a.Linv, (const double*)a.z, a.n_pose, (const double*)a.y_pose, (double*)a.delta, (double*)a.mcc_part, a.n_vis_blocks, a.small, a.n_small_units, a.up, a.first_update_block);
+  backsub_mcc_kernel_body((int)blockIdx.x, a.bsg_grid, a.n_lm, a.n_lm_groups, a.n_elim, a.n, (const int*)a.lm_start, (const double*)a.J, a.ja, (const double*)a.JB, (const double2*)a.r, (double*)a.CR, (const int*)a.cam_pose, (const int*)a.cp_tq, (const int*)a.cp_tp, (const double*)a.Linv, (const double*)a.z, a.n_pose, (const double*)a.y_pose, (double*)a.delta, (double*)a.mcc_part, a.n_vis_blocks, a.small, a.n_small_units, a.up, a.first_update_block);
 }
 
 // ---- the same launches over several windows (bsgpu_batch.cpp): one table entry per window, grids as the lone launches compute them
@@ -805,7 +826,7 @@ void batchargs_backsub_mcc(BatchArgTable& t, const Visual& v, int n_pose, const 
   const int extra = small ? (n_small_units + 1) / 2 : 0;
   const int upd_units = (upd && upd->n_blocks > 0) ? (upd->n_blocks + 255) / 256 : 0;
   a.bsg_grid = grid > 0 ? grid + extra + upd_units : 0;
-  a.n_lm = v.n_lm; a.n_lm_groups = g_lm; a.n_elim = v.n_elim; a.n = v.n; a.lm_start = v.lm_start; a.J = v.J; a.JB = v.JB; a.r = v.r; a.CR = v.no_cr ? nullptr : v.CR; a.cam_pose = v.cam_pose;
+  a.n_lm = v.n_lm; a.n_lm_groups = g_lm; a.n_elim = v.n_elim; a.n = v.n; a.lm_start = v.lm_start; a.J = v.J; a.ja = v.ja; a.JB = v.JB; a.r = v.r; a.CR = v.no_cr ? nullptr : v.CR; a.cam_pose = v.cam_pose;
   a.cp_tq = v.cp_tq; a.cp_tp = v.cp_tp; a.Linv = v.Linv; a.z = v.z; a.n_pose = n_pose; a.y_pose = y_pose; a.delta = delta; a.mcc_part = mcc_part; a.n_vis_blocks = grid;
   a.small = small ? *small : SmallGroupSet(); a.n_small_units = small ? n_small_units : 0; a.up = upd_units ? *upd : UpdateRide(); a.first_update_block = grid + extra;
   t.push(a);
@@ -817,9 +838,9 @@ void launch_backsub_mcc_batch(hipStream_t s, const BatchArgTable& t, const Batch
 int backsub_mcc_groups(const Visual& v) { return (v.n_lm * 8 + 255) / 256 + (v.n - v.n_elim + 255) / 256; }
 // ... with the model-cost terms of the window's dense prior (marg_body.h; they read the pose step only: the landmarks a prior names are not
 // eliminated) as the launch's last workgroups, four rows each, instead of marg_mcc_kernel behind it (4.6 us)
-__global__ __launch_bounds__(256) void backsub_mcc_marg_kernel(int n_lm, int n_lm_groups, int n_elim, int n, const int* __restrict__ lm_start, const double* __restrict__ J, const double* __restrict__ JB, const double2* __restrict__ r, const double* __restrict__ CR, const int* __restrict__ cam_pose, const int* __restrict__ cp_tq, const int* __restrict__ cp_tp, const double* __restrict__ Linv, const double* __restrict__ z, int n_pose, const double* __restrict__ y_pose, double* __restrict__ delta, double* __restrict__ mcc_part, int n_vis_blocks, SmallGroupSet small, int n_small_units, UpdateRide up, int first_update_block, MargDev m, double* __restrict__ marg_part, int first_marg_block) {
+__global__ __launch_bounds__(256) void backsub_mcc_marg_kernel(int n_lm, int n_lm_groups, int n_elim, int n, const int* __restrict__ lm_start, const double* __restrict__ J, int ja, const double* __restrict__ JB, const double2* __restrict__ r, const double* __restrict__ CR, const int* __restrict__ cam_pose, const int* __restrict__ cp_tq, const int* __restrict__ cp_tp, const double* __restrict__ Linv, const double* __restrict__ z, int n_pose, const double* __restrict__ y_pose, double* __restrict__ delta, double* __restrict__ mcc_part, int n_vis_blocks, SmallGroupSet small, int n_small_units, UpdateRide up, int first_update_block, MargDev m, double* __restrict__ marg_part, int first_marg_block) {
   if ((int)blockIdx.x >= first_marg_block) { marg_mcc_kernel_body(4 * ((int)blockIdx.x - first_marg_block), m, delta, marg_part); return; }
-  backsub_mcc_kernel_body((int)blockIdx.x, first_marg_block, n_lm, n_lm_groups, n_elim, n, lm_start, J, JB, r, CR, cam_pose, cp_tq, cp_tp, Linv, z, n_pose, y_pose, delta, mcc_part, n_vis_blocks, small, n_small_units, up, first_update_block);
+  backsub_mcc_kernel_body((int)blockIdx.x, first_marg_block, n_lm, n_lm_groups, n_elim, n, lm_start, J, ja, JB, r, CR, cam_pose, cp_tq, cp_tp, Linv, z, n_pose, y_pose, delta, mcc_part, n_vis_blocks, small, n_small_units, up, first_update_block);
 }
 bool launch_backsub_mcc(hipStream_t s, const Visual& v, int n_pose, const double* y_pose, double* delta, double* mcc_part,
                         const SmallGroupSet* small, int n_small_units, const UpdateRide* upd, const MargDev* marg, double* marg_part) {
@@ -829,12 +850,12 @@ bool launch_backsub_mcc(hipStream_t s, const Visual& v, int n_pose, const double
   const int upd_units = (upd && upd->n_blocks > 0) ? (upd->n_blocks + 255) / 256 : 0;
   if (marg && marg_part && marg->rows > 0) {
     const int own = grid + extra + upd_units;
-    hipLaunchKernelGGL(backsub_mcc_marg_kernel, dim3(own + (marg->rows + 3) / 4), dim3(256), 0, s, v.n_lm, g_lm, v.n_elim, v.n, v.lm_start, v.J, v.JB, v.r, v.no_cr ? nullptr : v.CR, v.cam_pose,
+    hipLaunchKernelGGL(backsub_mcc_marg_kernel, dim3(own + (marg->rows + 3) / 4), dim3(256), 0, s, v.n_lm, g_lm, v.n_elim, v.n, v.lm_start, v.J, v.ja, v.JB, v.r, v.no_cr ? nullptr : v.CR, v.cam_pose,
                        v.cp_tq, v.cp_tp, v.Linv, v.z, n_pose, y_pose, delta, mcc_part, grid, small ? *small : SmallGroupSet(), small ? n_small_units : 0,
                        upd_units ? *upd : UpdateRide(), grid + extra, *marg, marg_part, own);
     return true;
   }
-  hipLaunchKernelGGL(backsub_mcc_kernel, dim3(grid + extra + upd_units), dim3(256), 0, s, v.n_lm, g_lm, v.n_elim, v.n, v.lm_start, v.J, v.JB, v.r, v.no_cr ? nullptr : v.CR, v.cam_pose,
+  hipLaunchKernelGGL(backsub_mcc_kernel, dim3(grid + extra + upd_units), dim3(256), 0, s, v.n_lm, g_lm, v.n_elim, v.n, v.lm_start, v.J, v.ja, v.JB, v.r, v.no_cr ? nullptr : v.CR, v.cam_pose,
                      v.cp_tq, v.cp_tp, v.Linv, v.z, n_pose, y_pose, delta, mcc_part, grid, small ? *small : SmallGroupSet(), small ? n_small_units : 0,
                      upd_units ? *upd : UpdateRide(), grid + extra);
   return false;

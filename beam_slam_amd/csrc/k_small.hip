@@ -410,7 +410,7 @@ __global__ __launch_bounds__(64) void imu_eval_kernel(SmallGroup delta, SmallGro
 // factors, a wave each, per 256-thread workgroup): 5 us (cost only) / 10 us (with Jacobians) of a launch that nothing but the launch
 // order made wait for the reprojection factors.
 template <bool WITH_J>
-__device__ __forceinline__ void visual_imu_eval_kernel_body(const int bsg_bx, const int bsg_gx, SmallGroup delta, SmallGroup prior, double* __restrict__ part_delta, double* __restrict__ part_prior, int n_imu_blocks, int n, const int4* __restrict__ fac, const double2* __restrict__ pix, const double* __restrict__ wgt, const double* __restrict__ x, const DevCamera* __restrict__ cams, const DevLoss* __restrict__ losses, double2* __restrict__ r_out, double* __restrict__ J_out, double* __restrict__ JB_out, double* __restrict__ cost_part, int count_inactive) {
+__device__ __forceinline__ void visual_imu_eval_kernel_body(const int bsg_bx, const int bsg_gx, SmallGroup delta, SmallGroup prior, double* __restrict__ part_delta, double* __restrict__ part_prior, int n_imu_blocks, int n, const int4* __restrict__ fac, const double2* __restrict__ pix, const double* __restrict__ wgt, const double* __restrict__ x, const DevCamera* __restrict__ cams, const DevLoss* __restrict__ losses, double2* __restrict__ r_out, double* __restrict__ J_out, int ja, double* __restrict__ JB_out, double* __restrict__ cost_part, int count_inactive) {
   static_assert(kReprojStage<WITH_J> >= kImuStage<WITH_J, 4>, "the IMU units borrow the reprojection factors' staging area");
   __shared__ __attribute__((aligned(16))) double sJ[kReprojStage<WITH_J>];
   if (bsg_bx < n_imu_blocks) {
@@ -420,23 +420,23 @@ __device__ __forceinline__ void visual_imu_eval_kernel_body(const int bsg_bx, co
     else if (f < delta.n + prior.n) imu_prior_body<WITH_J>(prior, f - delta.n, x, losses, part_prior, lane);
     return;
   }
-  reproj_eval_body<WITH_J>(bsg_bx - n_imu_blocks, n, fac, pix, wgt, x, cams, losses, r_out, J_out, JB_out, cost_part, count_inactive, sJ);
+  reproj_eval_body<WITH_J>(bsg_bx - n_imu_blocks, n, fac, pix, wgt, x, cams, losses, r_out, J_out, ja, JB_out, cost_part, count_inactive, sJ);
 }
 template <bool WITH_J>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void visual_imu_eval_kernel(SmallGroup delta, SmallGroup prior, double* __restrict__ part_delta, double* __restrict__ part_prior, int n_imu_blocks, int n, const int4* __restrict__ fac, const double2* __restrict__ pix, const double* __restrict__ wgt, const double* __restrict__ x, const DevCamera* __restrict__ cams, const DevLoss* __restrict__ losses, double2* __restrict__ r_out, double* __restrict__ J_out, double* __restrict__ JB_out, double* __restrict__ cost_part, int count_inactive) {
-  visual_imu_eval_kernel_body<WITH_J>((int)blockIdx.x, (int)gridDim.x, delta, prior, part_delta, part_prior, n_imu_blocks, n, fac, pix, wgt, x, cams, losses, r_out, J_out, JB_out, cost_part, count_inactive);
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void visual_imu_eval_kernel(SmallGroup delta, SmallGroup prior, double* __restrict__ part_delta, double* __restrict__ part_prior, int n_imu_blocks, int n, const int4* __restrict__ fac, const double2* __restrict__ pix, const double* __restrict__ wgt, const double* __restrict__ x, const DevCamera* __restrict__ cams, const DevLoss* __restrict__ losses, double2* __restrict__ r_out, double* __restrict__ J_out, int ja, double* __restrict__ JB_out, double* __restrict__ cost_part, int count_inactive) {
+  visual_imu_eval_kernel_body<WITH_J>((int)blockIdx.x, (int)gridDim.x, delta, prior, part_delta, part_prior, n_imu_blocks, n, fac, pix, wgt, x, cams, losses, r_out, J_out, ja, JB_out, cost_part, count_inactive);
 }
 // The evaluation launched AHEAD of the accept / reject decision (residuals and Jacobians at the candidate, underneath the host's round trip)
 // with the end-of-step reduction of the step just computed as its first workgroups: the host's stamp leaves ~4 us into this launch
 // instead of after a launch of its own (7.7 us + the 4.5 us a kernel that wrote host memory takes to retire, on every LM step).
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void visual_imu_eval_reduce_kernel(ReduceRide red, SmallGroup delta, SmallGroup prior, double* __restrict__ part_delta, double* __restrict__ part_prior, int n_imu_blocks, int n, const int4* __restrict__ fac, const double2* __restrict__ pix, const double* __restrict__ wgt, const double* __restrict__ x, const DevCamera* __restrict__ cams, const DevLoss* __restrict__ losses, double2* __restrict__ r_out, double* __restrict__ J_out, double* __restrict__ JB_out, double* __restrict__ cost_part, int count_inactive) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void visual_imu_eval_reduce_kernel(ReduceRide red, SmallGroup delta, SmallGroup prior, double* __restrict__ part_delta, double* __restrict__ part_prior, int n_imu_blocks, int n, const int4* __restrict__ fac, const double2* __restrict__ pix, const double* __restrict__ wgt, const double* __restrict__ x, const DevCamera* __restrict__ cams, const DevLoss* __restrict__ losses, double2* __restrict__ r_out, double* __restrict__ J_out, int ja, double* __restrict__ JB_out, double* __restrict__ cost_part, int count_inactive) {
   const int n_units = red.n_slots + 1;
   if ((int)blockIdx.x < n_units) {
     __shared__ double sred[16];
     final_reduce_unit<256>((int)blockIdx.x, (int)threadIdx.x, red, n_units, sred);
     return;
   }
-  visual_imu_eval_kernel_body<true>((int)blockIdx.x - n_units, (int)gridDim.x - n_units, delta, prior, part_delta, part_prior, n_imu_blocks, n, fac, pix, wgt, x, cams, losses, r_out, J_out, JB_out, cost_part, count_inactive);
+  visual_imu_eval_kernel_body<true>((int)blockIdx.x - n_units, (int)gridDim.x - n_units, delta, prior, part_delta, part_prior, n_imu_blocks, n, fac, pix, wgt, x, cams, losses, r_out, J_out, ja, JB_out, cost_part, count_inactive);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
 struct visual_imu_eval_kernel_Args {
@@ -455,6 +455,7 @@ struct visual_imu_eval_kernel_Args {
   const DevLoss* losses;
   double2* r_out;
   double* J_out;
+  int ja;
   double* JB_out;
   double* cost_part;
   int count_inactive;
@@ -477,6 +478,7 @@ struct visual_imu_eval_kernel_ArgsG {
   const DevLoss __attribute__((address_space(1)))* losses;
   double2 __attribute__((address_space(1)))* r_out;
   double __attribute__((address_space(1)))* J_out;
+  int ja;
   double __attribute__((address_space(1)))* JB_out;
   double __attribute__((address_space(1)))* cost_part;
   int count_inactive;
@@ -488,27 +490,27 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.y];
   const visual_imu_eval_kernel_ArgsG& a = reinterpret_cast<const visual_imu_eval_kernel_ArgsG*>(bsg_A)[bsg_w];
   if ((int)blockIdx.x >= a.bsg_grid) return;
-  visual_imu_eval_kernel_body<WITH_J>((int)blockIdx.x, a.bsg_grid, a.delta, a.prior, (double*)a.part_delta, (double*)a.part_prior, a.n_imu_blocks, a.n, (const int4*)a.fac, (const double2*)a.pix, (const double*)a.wgt, (const double*)a.x, (const DevCamera*)a.cams, (const DevLoss*)a.losses, (double2*)a.r_out, (double*)a.J_out, (double*)a.JB_out, (double*)a.cost_part, a.count_inactive);
+  visual_imu_eval_kernel_body<WITH_J>((int)blockIdx.x, a.bsg_grid, a.delta, a.prior, (double*)a.part_delta, (double*)a.part_prior, a.n_imu_blocks, a.n, (const int4*)a.fac, (const double2*)a.pix, (const double*)a.wgt, (const double*)a.x, (const DevCamera*)a.cams, (const DevLoss*)a.losses, (double2*)a.r_out, (double*)a.J_out, a.ja, (double*)a.JB_out, (double*)a.cost_part, a.count_inactive);
 }
 void launch_visual_imu_eval(hipStream_t s, const Visual& v, const SmallGroup& delta, const SmallGroup& prior, const double* x, const DevCamera* cams,
                             const DevLoss* losses, bool with_J, double* cost_part_vis, double* part_delta, double* part_prior, const ReduceRide* red) {
   const int n_imu_blocks = (delta.n + prior.n + 3) / 4, grid = n_imu_blocks + (v.n + 255) / 256;
   if (with_J && red && red->n_entries > 0)
     hipLaunchKernelGGL(visual_imu_eval_reduce_kernel, dim3(red->n_slots + 1 + grid), dim3(256), 0, s, *red, delta, prior, part_delta, part_prior, n_imu_blocks, v.n,
-                       v.fac, v.pix, v.w, x, cams, losses, v.r, v.J, v.JB, cost_part_vis, 0);
+                       v.fac, v.pix, v.w, x, cams, losses, v.r, v.J, v.ja, v.JB, cost_part_vis, 0);
   else if (with_J)
     hipLaunchKernelGGL(visual_imu_eval_kernel<true>, dim3(grid), dim3(256), 0, s, delta, prior, part_delta, part_prior, n_imu_blocks, v.n, v.fac, v.pix, v.w,
-                       x, cams, losses, v.r, v.J, v.JB, cost_part_vis, 0);
+                       x, cams, losses, v.r, v.J, v.ja, v.JB, cost_part_vis, 0);
   else
     hipLaunchKernelGGL(visual_imu_eval_kernel<false>, dim3(grid), dim3(256), 0, s, delta, prior, part_delta, part_prior, n_imu_blocks, v.n, v.fac, v.pix, v.w,
-                       x, cams, losses, v.r, v.J, v.JB, cost_part_vis, 0);
+                       x, cams, losses, v.r, v.J, v.ja, v.JB, cost_part_vis, 0);
 }
 void batchargs_visual_imu_eval(BatchArgTable& t, const Visual& v, const SmallGroup& delta, const SmallGroup& prior, const double* x, const DevCamera* cams,
                                const DevLoss* losses, double* cost_part_vis, double* part_delta, double* part_prior) {
   visual_imu_eval_kernel_Args a;
   a.n_imu_blocks = (delta.n + prior.n + 3) / 4; a.bsg_grid = a.n_imu_blocks + (v.n + 255) / 256;
   a.delta = delta; a.prior = prior; a.part_delta = part_delta; a.part_prior = part_prior; a.n = v.n; a.fac = v.fac; a.pix = v.pix; a.wgt = v.w;
-  a.x = x; a.cams = cams; a.losses = losses; a.r_out = v.r; a.J_out = v.J; a.JB_out = v.JB; a.cost_part = cost_part_vis; a.count_inactive = 0;
+  a.x = x; a.cams = cams; a.losses = losses; a.r_out = v.r; a.J_out = v.J; a.ja = v.ja; a.JB_out = v.JB; a.cost_part = cost_part_vis; a.count_inactive = 0;
   t.push(a);
 }
 void launch_visual_imu_eval_batch(hipStream_t s, const BatchArgTable& t, const BatchDyn* dyn, int list, int n, bool with_J) {

@@ -8,7 +8,8 @@ namespace bsg {
 // ---------------------------------------------------------------------------------------------------
 // reprojection residual + Jacobian.  One factor per lane; the 2x9 Jacobian of a wave's 64 factors is
 // transposed through LDS so that the AoS rows leave as contiguous 16-byte-per-lane stores.
-// Algorithmic bytes per factor: 16 (idx+meta) + 16 (pixel) + 8 (w) in, 16 (r) + 144 (J) out = 200.
+// Algorithmic bytes per factor: 16 (idx+meta) + 16 (pixel) + 8 (w) in, 16 (r) + 144 (J) out = 200; with the compact pose part
+// (ja == kJACompact, bsgpu_internal.h) the translation columns are not stored: 16 + 96 out, 152.
 // ---------------------------------------------------------------------------------------------------
 // (the staging area is the caller's: the launch that also carries IMU factors lends the same bytes to their workgroups)
 template <bool WITH_J> constexpr int kReprojStage = WITH_J ? 4 * 64 * 18 : 4;
@@ -16,8 +17,8 @@ template <bool WITH_J>
 __device__ __forceinline__ void reproj_eval_body(const int block, int n, const int4* __restrict__ fac, const double2* __restrict__ pix,
                                                  const double* __restrict__ wgt, const double* __restrict__ x,
                                                  const DevCamera* __restrict__ cams, const DevLoss* __restrict__ losses,
-                                                 double2* __restrict__ r_out, double* __restrict__ J_out, double* __restrict__ JB_out,
-                                                 double* __restrict__ cost_part, int count_inactive, double* sJ /* kReprojStage<WITH_J> doubles of LDS, 16-byte aligned */) {
+                                                 double2* __restrict__ r_out, double* __restrict__ J_out, int ja /* Visual::ja */,
+                                                 double* __restrict__ JB_out, double* __restrict__ cost_part, int count_inactive, double* sJ /* kReprojStage<WITH_J> doubles of LDS, 16-byte aligned */) {
   __shared__ double sred[4];
   const int f = block * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -100,29 +101,48 @@ __device__ __forceinline__ void reproj_eval_body(const int block, int n, const i
   const double tot = block_sum_256(cost, sred);
   if (threadIdx.x == 0) cost_part[block] = tot;
   if (WITH_J) {
+    typedef double d2_t __attribute__((ext_vector_type(2)));
+    const bool compact = ja == kJACompact;   // (the same in every lane of the launch)
     double* sw = sJ + wave * (64 * 18);
-#pragma unroll
     // stored row: [A row 0 (q, p: 6) | A row 1 (6) | B row 0 (landmark: 3) | B row 1 (3)] — the pose part contiguous for the pair
-    // kernel and the back-substitution, the landmark part contiguous for the landmark kernel (J[] above is [q p l | q p l])
-    for (int i = 0; i < 18; ++i) { const int rw = i / 9, cl = i % 9; sw[lane * 18 + (cl < 6 ? 6 * rw + cl : 12 + 3 * rw + (cl - 6))] = J[i]; }
+    // kernel and the back-substitution, the landmark part contiguous for the landmark kernel (J[] above is [q p l | q p l]).
+    // Compact: [theta row 0 (3) | theta row 1 (3) | B row 0 | B row 1 | pad 2] — seven 16-byte pieces per factor in the stage (an odd
+    // number, as the full layout's nine); the p columns are -B and are not stored.
+    if (compact) {
+#pragma unroll
+      for (int i = 0; i < 18; ++i) { const int rw = i / 9, cl = i % 9; if (cl < 3 || cl >= 6) sw[lane * 14 + (cl < 3 ? 3 * rw + cl : 6 + 3 * rw + (cl - 6))] = J[i]; }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 18; ++i) { const int rw = i / 9, cl = i % 9; sw[lane * 18 + (cl < 6 ? 6 * rw + cl : 12 + 3 * rw + (cl - 6))] = J[i]; }
+    }
     __syncthreads();
     const int fb = block * 256 + wave * 64;
     const int cnt = min(64, n - fb);
     if (cnt > 0) {
-      // two contiguous streams per wave: 96 B of pose part and 48 B of landmark part per factor, 16 B per lane and store
-      typedef double d2_t __attribute__((ext_vector_type(2)));
-      d2_t* dstA = reinterpret_cast<d2_t*>(J_out + (size_t)fb * kJAStride);
+      // two contiguous streams per wave: 96 B (compact: 48 B) of pose part and 48 B of landmark part per factor, 16 B per lane and store
+      d2_t* dstA = reinterpret_cast<d2_t*>(J_out + (size_t)fb * (compact ? kJACompact : kJAStride));
       d2_t* dstB = reinterpret_cast<d2_t*>(JB_out + (size_t)fb * 6);
       const d2_t* src = reinterpret_cast<const d2_t*>(sw);
+      if (compact) {
 #pragma unroll
-      for (int it = 0; it < 6; ++it) {
-        const int e = it * 64 + lane;
-        if (e < cnt * 6) __builtin_nontemporal_store(src[(e / 6) * 9 + (e % 6)], &dstA[(e / 6) * (kJAStride / 2) + (e % 6)]);   // streamed: no cache holds 58 MB until the next kernel
-      }
+        for (int it = 0; it < 3; ++it) {
+          const int e = it * 64 + lane;
+          if (e < cnt * 3) {
+            __builtin_nontemporal_store(src[(e / 3) * 7 + (e % 3)], &dstA[e]);
+            __builtin_nontemporal_store(src[(e / 3) * 7 + 3 + (e % 3)], &dstB[e]);
+          }
+        }
+      } else {
 #pragma unroll
-      for (int it = 0; it < 3; ++it) {
-        const int e = it * 64 + lane;
-        if (e < cnt * 3) __builtin_nontemporal_store(src[(e / 3) * 9 + 6 + (e % 3)], &dstB[e]);
+        for (int it = 0; it < 6; ++it) {
+          const int e = it * 64 + lane;
+          if (e < cnt * 6) __builtin_nontemporal_store(src[(e / 6) * 9 + (e % 6)], &dstA[(e / 6) * (kJAStride / 2) + (e % 6)]);   // streamed: no cache holds 58 MB until the next kernel
+        }
+#pragma unroll
+        for (int it = 0; it < 3; ++it) {
+          const int e = it * 64 + lane;
+          if (e < cnt * 3) __builtin_nontemporal_store(src[(e / 3) * 9 + 6 + (e % 3)], &dstB[e]);
+        }
       }
     }
   }
