@@ -169,8 +169,9 @@ int bsgpu_set_values(bsgpu_ctx* c, const double* v, int64_t n) try {
   if ((size_t)n != c->h_x.size()) return fail(c, BSGPU_ERR_INVALID, "set_values: size mismatch");
   c->h_x.assign(v, v + n);
   if (c->finalized) {
-    // derived cameras depend on constant extrinsic values: re-finalize if any online-calib factor exists
-    if (c->groups[BSGPU_F_REPROJ_ONLINE_CALIB].n) { c->finalized = false; return BSGPU_OK; }
+    // derived cameras depend on constant extrinsic values: re-finalize if any online-calib factor names a constant pair (the entries of
+    // a free pair are rebuilt from the values before every evaluation, k_calib.hip)
+    if (c->groups[BSGPU_F_REPROJ_ONLINE_CALIB].n && (c->oc_const_pair || !c->calib.on)) { c->finalized = false; return BSGPU_OK; }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpy(c->d_x, v, sizeof(double) * n, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(c->d_x0, v, sizeof(double) * n, hipMemcpyHostToDevice));
@@ -522,6 +523,11 @@ int bsgpu_evaluate(bsgpu_ctx* c, double* cost, double* residuals, double* gradie
     HIPCHK(c, hipMemcpy(lm_of.data(), V.lm_of, sizeof(int) * V.n, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(cp_tq.data(), V.cp_tq, sizeof(int) * V.n_cam_pose, hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(cp_tp.data(), V.cp_tp, sizeof(int) * V.n_cam_pose, hipMemcpyDeviceToHost));
+    std::vector<double> E;   // (a free extrinsic pair: the factors' columns of its two blocks, k_calib.hip)
+    if (c->calib.on) {
+      E.resize((size_t)V.n * 12);
+      HIPCHK(c, hipMemcpy(E.data(), c->calib.E, sizeof(double) * E.size(), hipMemcpyDeviceToHost));
+    }
     for (int i = 0; i < V.n; ++i) {
       const int t = c->vis_src[i] >> 28, f = c->vis_src[i] & ((1 << 28) - 1);
       const int row = c->row0[t] + 2 * f;
@@ -537,6 +543,17 @@ int bsgpu_evaluate(bsgpu_ctx* c, double* cost, double* residuals, double* gradie
             const double v = sl == 2 ? vb : V.ja == kJAStride ? J[(size_t)i * kJAStride + 6 * k + 3 * sl + j] : sl == 0 ? J[(size_t)i * kJACompact + 3 * k + j] : -vb;
             grad[cols[sl] + j] += v * r[2 * (size_t)i + k];
             if (jacobian) jacobian[(size_t)(row + k) * n + cols[sl] + j] = v;
+          }
+        }
+        if (t == BSGPU_F_REPROJ_ONLINE_CALIB && !E.empty()) {
+          const int ce[2] = {c->calib.tq, c->calib.tp};
+          for (int sl = 0; sl < 2; ++sl) {
+            if (ce[sl] < 0) continue;
+            for (int j = 0; j < 3; ++j) {
+              const double v = E[(size_t)i * 12 + 6 * k + 3 * sl + j];
+              grad[ce[sl] + j] += v * r[2 * (size_t)i + k];
+              if (jacobian) jacobian[(size_t)(row + k) * n + ce[sl] + j] = v;
+            }
           }
         }
       }
@@ -603,6 +620,7 @@ int bsgpu_marginalize(bsgpu_ctx* c, int32_t n_marg, const int32_t* marg_blocks, 
   if (!marg_blocks || n_marg <= 0 || !n_kept || !n_rows || !n_cols) return fail(c, BSGPU_ERR_INVALID, "marginalize: bad arguments");
   int rc = finalize(c);
   if (rc != BSGPU_OK) return rc;
+  if (c->calib.on) return fail(c, BSGPU_ERR_UNSUPPORTED, "marginalize: not supported on a window with a free extrinsic pair (online calibration)");
   if ((rc = materialize_mirror(c)) != BSGPU_OK) return rc;   // (the factors touching the blocks are picked from the host rows)
   c->marg_result = bsgpu_ctx::MargResult();
   const int nb = c->nb;
@@ -828,6 +846,9 @@ int bsgpu_covariance_requests(bsgpu_ctx* c, int32_t n_req, const int32_t* pairs,
     const int b = pairs[i];
     if (b < 0 || b >= c->nb) return fail(c, BSGPU_ERR_INVALID, "covariance_requests: block out of range");
     if (c->toff[b] < 0) return fail(c, BSGPU_ERR_INVALID, "covariance_requests: constant block");
+    if (c->calib.on && c->is_lm[b])
+      return fail(c, BSGPU_ERR_UNSUPPORTED, "covariance_requests: an eliminated landmark of a window with a free extrinsic pair (online calibration): "
+                                            "pose-side blocks only");
   }
   std::vector<int64_t> off(n_req + 1, 0);
   for (int i = 0; i < n_req; ++i) off[i + 1] = off[i] + (int64_t)c->tsize[pairs[2 * i]] * c->tsize[pairs[2 * i + 1]];
@@ -960,6 +981,7 @@ int bsgpu_reprojection_errors(bsgpu_ctx* c, double* err) try {
   if (V.n + D.n == 0) return BSGPU_OK;
   double* d_out = nullptr;
   HIPCHK(c, hipMalloc((void**)&d_out, sizeof(double) * (size_t)(V.n + D.n)));
+  if (c->calib.on) launch_calib_refresh(c->stream, c->calib, c->d_x, c->d_cams);   // (a free extrinsic pair: at its current values)
   launch_reproj_errors(c->stream, V, D, c->d_x, c->d_cams, d_out, d_out + V.n);
   std::vector<double> h((size_t)V.n + D.n);
   const hipError_t e = hipMemcpyAsync(h.data(), d_out, sizeof(double) * h.size(), hipMemcpyDeviceToHost, c->stream);

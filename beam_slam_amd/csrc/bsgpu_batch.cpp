@@ -70,6 +70,7 @@ bool batch_covers(bsgpu_ctx* c, const bsgpu_options& o) {
   if (!c->finalized) return false;
   if (!(o.linear_solver_type == BSGPU_LINEAR_AUTO || o.linear_solver_type == BSGPU_LINEAR_SCHUR_CHOLESKY)) return false;
   if (o.trust_region_strategy_type != BSGPU_TR_LEVENBERG_MARQUARDT) return false;   // (DOGLEG: bsgpu_solve on a thread of its own)
+  if (c->calib.on) return false;   // (a free extrinsic pair: bsgpu_solve on a thread of its own — the batched launches carry no border)
   if (!c->dense_ok || c->use_graphs || !c->d_S || !c->h_scal_dev || !c->d_reduce_counter || c->n_reduce <= 0 || c->n_pose <= 0) return false;
   {   // at most ONE dense prior with free blocks (a window after a slide with true marginalisation), narrow enough for the one-launch evaluation
     int n_act = 0;

@@ -158,6 +158,8 @@ struct bsgpu_ctx {
   Visual vis;
   IdpElim idp;                   // inverse-depth landmarks eliminated on the landmark side (bsgpu_finalize.cpp, k_idp.hip)
   int n_idp_lm = 0;
+  bool oc_const_pair = false;    // some online-calibration factor names a constant extrinsic pair: its derived camera is folded at finalize()
+  Calib calib;                   // the free extrinsic pair of the online-calibration factors, if any (bsgpu_finalize.cpp, k_calib.hip)
   SmallGroup small[kNumInternal];
   std::vector<unsigned char> h_small_active[kNumInternal];
   unsigned char* d_small_inactive[kNumInternal] = {nullptr};
@@ -326,6 +328,7 @@ struct bsgpu_ctx {
     if (pool_bytes > ((size_t)8 << 30)) release_pool();
     vis = Visual();
     idp = IdpElim();
+    calib = Calib();
     for (auto& g : small) g = SmallGroup();
     d_x = d_xcand = d_x0 = nullptr;
     d_dl_g = d_dl_v = d_dl_gn = d_dl_part = d_dl_scal = nullptr;

@@ -222,6 +222,24 @@ int finalize(bsgpu_ctx* c) {
     cams.push_back(d);
   }
   std::map<std::tuple<int, int, int>, int> derived_cam;
+  // ---- online calibration: the extrinsic pair of the type-1 factors that is not constant (both blocks, or one of them).  Its derived camera
+  // entries are rebuilt on the device before every evaluation (k_calib.hip), its tangent columns are a border of the reduced system.
+  int calib_bq = -1, calib_bp = -1;
+  c->oc_const_pair = false;
+  {
+    const HostGroup& g = c->groups[BSGPU_F_REPROJ_ONLINE_CALIB];
+    const int ni = kTypes[BSGPU_F_REPROJ_ONLINE_CALIB].nidx;
+    for (int f = 0; f < g.n; ++f) {
+      const int bqe = g.idx[(size_t)f * ni + 3], bpe = g.idx[(size_t)f * ni + 4];
+      if (c->is_const[bqe] && c->is_const[bpe]) { c->oc_const_pair = true; continue; }
+      if (calib_bq < 0) { calib_bq = bqe; calib_bp = bpe; }
+      else if (calib_bq != bqe || calib_bp != bpe)
+        return fail(c, BSGPU_ERR_UNSUPPORTED, "online-calibration reprojection factors with more than one free extrinsic pair (one pair of "
+                                              "q_BASELINK_CAM / p_BASELINK_CAM blocks per window can be estimated)");
+    }
+  }
+  const bool has_calib = calib_bq >= 0;
+  std::vector<int> calib_cams;  // derived camera entries of the free pair
 
   // band landmarks on the matrix cores (k_band.hip) in windows of at least kBandMinFactors reprojection factors: a unit of that kernel is a
   // first camera pose's landmarks, and a window of the reference's own size has too few of them per pose to fill the device (measured,
@@ -230,7 +248,8 @@ int finalize(bsgpu_ctx* c) {
   const char* band_env = getenv("BSGPU_PAIRS_BAND");
   const int n_reproj = c->groups[BSGPU_F_REPROJ].n + c->groups[BSGPU_F_REPROJ_ONLINE_CALIB].n;
   // (band_available(): the kernel's ~147 KB of dynamic LDS per workgroup, asked of this device once — a device or partition without it keeps the pair entries)
-  const bool band_on = (band_env ? strcmp(band_env, "0") != 0 : n_reproj >= kBandMinFactors) && band_available();
+  // (a free extrinsic pair: the border kernels read the C rows and the full pose part, which only the pair-entry form keeps — k_calib.hip)
+  const bool band_on = !has_calib && (band_env ? strcmp(band_env, "0") != 0 : n_reproj >= kBandMinFactors) && band_available();
   const bool sort_entries = getenv("BSGPU_PAIR_ENTRIES_SORT") != nullptr;   // (tests: the path windows of more than 2 896 camera poses take)
   // ---- visual factors: camera-pose ids, factors sorted by landmark, pair entries, tile adjacency.
   // Large plain windows are flattened on the device (k_flatten.hip); everything else — and any window the device
@@ -244,7 +263,7 @@ int finalize(bsgpu_ctx* c) {
   c->d_vis_src = nullptr;
   auto host_visual = [&]() -> int {
   { const int rc_m = materialize_mirror(c); if (rc_m != BSGPU_OK) return rc_m; }
-  struct VF { int xq, xp, xl, bq, bp, meta_cam, loss, flags, lm, src; double u, v, w; };
+  struct VF { int xq, xp, xl, bq, bp, meta_cam, loss, flags, lm, src; double u, v, w; int calib; };
   std::vector<VF> vf;
   for (int t = 0; t <= 1; ++t) {
     const HostGroup& g = c->groups[t];
@@ -255,12 +274,10 @@ int finalize(bsgpu_ctx* c) {
       e.bq = idx[0]; e.bp = idx[1];
       e.xq = c->off[idx[0]]; e.xp = c->off[idx[1]]; e.xl = c->off[idx[2]];
       int cam = idx[ti.nvar];
+      e.calib = 0;
       if (t == 1) {
         const int bqe = idx[3], bpe = idx[4];
-        if (!c->is_const[bqe] || !c->is_const[bpe])
-          return fail(c, BSGPU_ERR_UNSUPPORTED,
-                      "online-calibration reprojection factor with non-constant extrinsic blocks (the reference holds "
-                      "them constant: bs_variables/src/orientation_3d.cpp:39-41)");
+        e.calib = (!c->is_const[bqe] || !c->is_const[bpe]) ? 1 : 0;   // (the free pair: its entry is the current values', rebuilt before every evaluation)
         auto key = std::make_tuple(bqe, bpe, cam);
         auto it = derived_cam.find(key);
         if (it == derived_cam.end()) {
@@ -273,6 +290,7 @@ int finalize(bsgpu_ctx* c) {
           for (int i = 0; i < 3; ++i) d.t[i] = -(d.R[3 * i] * pbc[0] + d.R[3 * i + 1] * pbc[1] + d.R[3 * i + 2] * pbc[2]);
           cams.push_back(d);
           it = derived_cam.emplace(key, (int)cams.size() - 1).first;
+          if (e.calib) calib_cams.push_back(it->second);
         }
         cam = it->second;
       }
@@ -280,9 +298,16 @@ int finalize(bsgpu_ctx* c) {
       e.loss = get_loss(g.loss_kind[f], g.loss_a[f]);
       e.flags = (c->is_const[idx[0]] ? kFlagQConst : 0) | (c->is_const[idx[1]] ? kFlagPConst : 0) |
                 (c->is_const[idx[2]] ? kFlagLConst : 0);
+      // (such a factor's cost would be summed by the fixed-cost pass — once per solve, as a constant, from camera entries nobody refreshed
+      //  for it — although it depends on the pair)
+      if (e.calib && e.flags == 7)
+        return fail(c, BSGPU_ERR_UNSUPPORTED, "online-calibration reprojection factor with a free extrinsic pair whose pose and landmark blocks are all constant");
       if (e.flags == 7) { c->any_inactive = true; c->vis_any_inactive = true; }
       e.lm = lm_index[idx[2]];
       e.src = (t << 28) | f;
+      if (e.calib && e.lm < 0 && !c->is_const[idx[2]])
+        return fail(c, BSGPU_ERR_UNSUPPORTED, "online-calibration reprojection factor with a free extrinsic pair whose landmark block is not eliminated "
+                                              "(it is shared with another kind of factor)");
       if (e.lm < 0 && !c->is_const[idx[2]]) {
         // the landmark block is not eliminated (it is shared with another kind of factor): pose-only style group
         HostGroup& dg = c->groups[T_REPROJ_DENSE];
@@ -453,6 +478,37 @@ int finalize(bsgpu_ctx* c) {
         const int ri[2] = {cp_tq[i], cp_tp[i]}, rj[2] = {cp_tq[j], cp_tp[j]};
         for (int a = 0; a < 2; ++a) for (int b = 0; b < 2; ++b) touch(ri[a], rj[b]);
       }
+    if (has_calib) {
+      // the free extrinsic pair: which factors name it, every factor by camera pose (S(i,e) is summed per camera pose: a factor of another
+      // kind on a landmark the pair's factors see has E~ = -C G too), and the border's tiles: the pair with every camera pose and with itself
+      Calib& cb = c->calib;
+      cb.on = 1;
+      cb.xq = c->off[calib_bq]; cb.xp = c->off[calib_bp];
+      cb.tq = c->toff[calib_bq]; cb.tp = c->toff[calib_bp];   // (-1: that block is constant)
+      cb.n_cam = (int)calib_cams.size();
+      cb.cam_id = c->upload(calib_cams);
+      std::vector<unsigned char> has(std::max(1, nv), 0);
+      for (int i = 0; i < nv; ++i) has[i] = vf[i].calib ? 1 : 0;
+      cb.has = c->upload(has);
+      std::vector<int> cnt(k + 1, 0), by_cp(nv);
+      for (int i = 0; i < nv; ++i) cnt[cam_pose[i] + 1]++;
+      for (int i = 0; i < k; ++i) cnt[i + 1] += cnt[i];
+      {
+        std::vector<int> pos(cnt.begin(), cnt.end() - 1);
+        for (int i = 0; i < nv; ++i) by_cp[pos[cam_pose[i]]++] = i;
+      }
+      std::vector<int> sg_cp, sg_start;
+      for (int i = 0; i < k; ++i)
+        for (int p0 = cnt[i]; p0 < cnt[i + 1]; p0 += 256) { sg_cp.push_back(i); sg_start.push_back(p0); }
+      sg_start.push_back(nv);
+      cb.n_seg = (int)sg_cp.size();
+      cb.seg_cp = c->upload(sg_cp); cb.seg_start = c->upload(sg_start); cb.seg_fac = c->upload(by_cp);
+      const int re[2] = {cb.tq, cb.tp};
+      for (int a = 0; a < 2; ++a) {
+        for (int b = 0; b < 2; ++b) touch(re[a], re[b]);
+        for (int i = 0; i < k; ++i) { touch(cp_tq[i], re[a]); touch(cp_tp[i], re[a]); }
+      }
+    }
   }
     return BSGPU_OK;
   };
@@ -511,6 +567,11 @@ int finalize(bsgpu_ctx* c) {
     V.cost_part_cand = c->alloc<double>(V.n_cost_part);
     V.mcc_part = c->alloc<double>(std::max(1, backsub_mcc_groups(V)));
     if (!V.J || !V.CR || !V.r) return fail(c, BSGPU_ERR_DEVICE, "out of device memory (visual tables)");
+    if (c->calib.on) {
+      c->calib.E = c->alloc<double>((size_t)std::max(1, nv) * 12); c->calib.Et = c->alloc<double>((size_t)std::max(1, nv) * 12);
+      c->calib.part = c->alloc<double>((size_t)std::max(1, calib_border_blocks(V)) * kCalibPartStride);
+      if (!c->calib.E || !c->calib.Et || !c->calib.part) return fail(c, BSGPU_ERR_DEVICE, "out of device memory (extrinsic border tables)");
+    }
     // (bsgpu_internal.h Visual::no_cr: every factor belongs to a band landmark)
     const char* no_cr_env = getenv("BSGPU_NO_CR");
     V.no_cr = !(no_cr_env && atoi(no_cr_env) == 0) && V.n_band_units > 0 && V.n_seg == 0 && V.n_ent == 0 && V.n == V.n_elim && V.band_lm_id != nullptr && V.Linv && V.z;
@@ -1160,14 +1221,14 @@ int finalize(bsgpu_ctx* c) {
   chol_prepare();
   // hipGraph replay of the LM step is opt-in (BSGPU_GRAPH=1): on ROCm 7.2 the replay inserts a ~0.9 ms bubble
   // inside the long dependent kernel chain (profiles/README.md), which cancels what it saves on launches
-  c->use_graphs = getenv("BSGPU_GRAPH") != nullptr;
+  c->use_graphs = getenv("BSGPU_GRAPH") != nullptr && !c->calib.on;   // (a free extrinsic pair: host-decided eager steps)
   HIPCHK(c, hipMemset(c->d_scal, 0, sizeof(double) * SC_NUM));
   HIPCHK(c, hipMemset(c->d_delta, 0, sizeof(double) * std::max(1, c->n_tan)));
   lap("blocks + dense buffers");
   {
     c->n_part_upd = (nb + 255) / 256;
     c->n_upd_blocks = 0; c->d_upd_blocks = nullptr; c->d_lm_xoff = nullptr;
-    if (c->vis.n_lm > 0 && !getenv("BSGPU_UPDATE_SEPARATE")) {
+    if (c->vis.n_lm > 0 && !getenv("BSGPU_UPDATE_SEPARATE") && !c->calib.on) {   // (a free extrinsic pair: its back-substitution carries no riders, k_calib.hip)
       // the candidate update rides in the landmark back-substitution (k_reproj.hip: backsub_mcc_kernel): the eliminated Euclidean landmarks
       // are updated by the lanes that compute their step, every other block by extra workgroups of that launch
       std::vector<int> others, lm_xoff(c->vis.n_lm, 0);

@@ -170,6 +170,30 @@ struct Visual {
   int n_cost_part = 0;
 };
 
+// The free extrinsic pair (q_BASELINK_CAM, p_BASELINK_CAM) of a window's online-calibration reprojection factors (k_calib.hip): its
+// tangent columns are pose-side columns every such factor touches — a border of the reduced system.  on == 0: no such pair, and none of
+// that file's launches is issued.
+constexpr int kCalibPartStride = 40;
+struct Calib {
+  int on = 0;
+  int xq = 0, xp = 0;                    // offsets of the two blocks in x
+  int tq = -1, tp = -1;                  // their tangent offsets (-1: that block is constant)
+  int n_cam = 0;                         // derived camera-table entries of the pair (one per camera it is used with)
+  const int* cam_id = nullptr;           // ... their positions in the camera table
+  const unsigned char* has = nullptr;    // per visual factor (sorted order): 1 = it names the pair
+  double* E = nullptr;                   // n x 12: [E row 0 (theta: 3, p: 3) | E row 1], zero for the other factors
+  double* Et = nullptr;                  // n x 12: E~ = E - C G_l
+  double* part = nullptr;                // calib_border_blocks() x kCalibPartStride: the border's own sums per workgroup of calib_border_kernel
+  int n_seg = 0;                         // the visual factors by camera pose, in segments of at most 256 (calib_pose_kernel)
+  const int* seg_cp = nullptr; const int* seg_start = nullptr; const int* seg_fac = nullptr;
+};
+void launch_calib_refresh(hipStream_t s, const Calib& cb, const double* x, DevCamera* cams);
+void launch_calib_E(hipStream_t s, const Visual& v, const Calib& cb, const double* x, const DevCamera* cams, const DevLoss* losses);
+int calib_border_blocks(const Visual& v);
+void launch_calib_border(hipStream_t s, const Visual& v, const Calib& cb, double* S, int ld, int rhs_row, double* grad, double* hdiag, const int* perm,
+                         bool grad_only);
+void launch_calib_backsub_mcc(hipStream_t s, const Visual& v, const Calib& cb, int n_pose, const double* y_pose, double* delta, double* mcc_part);
+
 // inverse-depth landmarks eliminated on the landmark side (k_idp.hip): the binary inverse-depth factors (SmallGroup of
 // BSGPU_F_IDP_REPROJ: r, J 2 x 15 from idp_kernel) sorted by their scalar landmark; a VIEW is one (landmark, camera pose) pair — the
 // anchor pose once per landmark, every measurement pose once — and carries u = sum A^T c over the factors of the landmark that see it

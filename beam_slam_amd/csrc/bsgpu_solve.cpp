@@ -206,12 +206,15 @@ void eval_all(bsgpu_ctx* c, const double* x, bool with_J, int slot, const Reduce
   // unless BSGPU_EVAL_MERGE=0: there the IMU body's registers cost the reprojection kernel a wave of occupancy per SIMD)
   static const int merge_mode = getenv("BSGPU_EVAL_MERGE") ? atoi(getenv("BSGPU_EVAL_MERGE")) : 2;   // 0: never, 1: cost-only passes, 2: both
   const bool merged = imu_pair && c->vis.n > 0 && (with_J ? merge_mode >= 2 : merge_mode >= 1);
+  // (a free extrinsic pair: its derived camera entries from the values this evaluation reads, so that the kernels below stay as they are)
+  if (c->calib.on) launch_calib_refresh(s, c->calib, x, c->d_cams);
   if (merged)
     launch_visual_imu_eval(s, c->vis, c->small[BSGPU_F_IMU_DELTA], c->small[BSGPU_F_IMU_PRIOR], x, c->d_cams, c->d_losses, with_J,
                            cand ? c->vis.cost_part_cand : c->vis.cost_part,
                            cand ? c->d_small_part_cand[BSGPU_F_IMU_DELTA] : c->d_small_part[BSGPU_F_IMU_DELTA],
                            cand ? c->d_small_part_cand[BSGPU_F_IMU_PRIOR] : c->d_small_part[BSGPU_F_IMU_PRIOR], red);
   else if (c->vis.n) launch_reproj_eval(s, c->vis, x, c->d_cams, c->d_losses, with_J, cand ? c->vis.cost_part_cand : c->vis.cost_part);
+  if (c->calib.on && with_J) launch_calib_E(s, c->vis, c->calib, x, c->d_cams, c->d_losses);   // (... and the factors' extrinsic columns)
   if (with_J) phase_mark(c, BSGPU_PHASE_EVAL_REPROJ);
   // (a lidar-inertial window: they ride in the relative-pose evaluation instead)
   int rel_t = -1;
@@ -337,6 +340,8 @@ void assemble(bsgpu_ctx* c, const bsgpu_options& o, double radius, bool new_J, b
     const bool lower_only = !lower_off && factor_follows && !gradient_only && !c->use_spcg && !c->use_pcg && c->dense_ok && c->d_ftasks && c->d_fsync && c->d_tile_tot && c->d_Winv;
     if (band) launch_pairs_band(s, c->vis, c->d_S, c->npad, c->plan.rhs_row, c->d_grad, c->d_hdiag, c->d_dpos, gradient_only, units > 0 ? &set : nullptr, units, lower_only, go);
     launch_pairs(s, c->vis, c->d_S, c->npad, c->plan.rhs_row, c->d_grad, c->d_hdiag, c->d_dpos, gradient_only, (units > 0 && !band) ? &set : nullptr, band ? 0 : units, go);
+    // (a free extrinsic pair: the border S(i,e), S(e,e), rhs(e), g_e, diag(H)_e — behind the landmark launch, whose C rows it reads)
+    if (c->calib.on) launch_calib_border(s, c->vis, c->calib, c->d_S, c->npad, c->plan.rhs_row, c->d_grad, c->d_hdiag, c->d_dpos, gradient_only);
     phase_mark(c, BSGPU_PHASE_PAIRS);
     // (... or, without a pair launch, in the launch of the segment-wise assembled groups)
     SmallGroupSet set2;
@@ -468,15 +473,19 @@ void linear_solve_and_candidate(bsgpu_ctx* c, const bsgpu_options& o, bool defer
     // there is no visual launch, go by themselves)
     SmallGroupSet set;
     int taken = 0, units = 0;
-    if (backsub_mcc_groups(c->vis) > 0) units = small_mcc_first_set(c->small + 2, c->d_small_part_mcc + 2, kNumInternal - 2, &set, &taken);
+    // (a free extrinsic pair: the back-substitution with the E y_e terms, k_calib.hip — no riders; the pose-only groups' terms, the dense
+    //  prior's and the update take their own launches below)
+    const bool calib = c->calib.on && backsub_mcc_groups(c->vis) > 0;
+    if (backsub_mcc_groups(c->vis) > 0 && !calib) units = small_mcc_first_set(c->small + 2, c->d_small_part_mcc + 2, kNumInternal - 2, &set, &taken);
     UpdateRide up;
     if (c->n_upd_blocks > 0) {
       up.n_blocks = c->n_upd_blocks; up.blocks = c->d_upd_blocks; up.xoff = c->d_blk_xoff; up.toff = c->d_blk_toff; up.size = c->d_blk_size;
       up.manifold = c->d_blk_manifold; up.lm_xoff = c->d_lm_xoff; up.x = c->d_x; up.x_cand = c->d_xcand; up.part = c->d_part_upd;
     }
     const int mr = marg_rider(c);
-    if (launch_backsub_mcc(s, c->vis, c->n_pose, c->d_ytan, c->d_delta, c->vis.mcc_part, units > 0 ? &set : nullptr, units, c->n_upd_blocks > 0 ? &up : nullptr,
-                           mr >= 0 ? &c->marg[mr].dev : nullptr, mr >= 0 ? c->marg[mr].part_mcc : nullptr))
+    if (calib) launch_calib_backsub_mcc(s, c->vis, c->calib, c->n_pose, c->d_ytan, c->d_delta, c->vis.mcc_part);
+    else if (launch_backsub_mcc(s, c->vis, c->n_pose, c->d_ytan, c->d_delta, c->vis.mcc_part, units > 0 ? &set : nullptr, units, c->n_upd_blocks > 0 ? &up : nullptr,
+                                mr >= 0 ? &c->marg[mr].dev : nullptr, mr >= 0 ? c->marg[mr].part_mcc : nullptr))
       marg_mcc_done = mr;
     if (units == 0) taken = 0;
     UpdateRide all;
@@ -993,6 +1002,13 @@ int solve(bsgpu_ctx* c, const bsgpu_options& o, bsgpu_summary& sum) {
   int rc = finalize(c);
   if (rc != BSGPU_OK) return rc;
   if ((rc = check_strategy(c, o)) != BSGPU_OK) return rc;
+  if (c->calib.on) {   // a free extrinsic pair: LM on the exact path (k_calib.hip assembles the border of the dense reduced system only)
+    if (o.trust_region_strategy_type != BSGPU_TR_LEVENBERG_MARQUARDT)
+      return fail(c, BSGPU_ERR_UNSUPPORTED, "DOGLEG: not supported on a window with a free extrinsic pair (online calibration)");
+    if (o.linear_solver_type == BSGPU_LINEAR_PCG || o.linear_solver_type == BSGPU_LINEAR_SCHUR_PCG || !c->dense_ok)
+      return fail(c, BSGPU_ERR_UNSUPPORTED, "a window with a free extrinsic pair (online calibration) is solved on the exact path: not "
+                                            "BSGPU_LINEAR_PCG / BSGPU_LINEAR_SCHUR_PCG");
+  }
   HIPCHK(c, hipSetDevice(c->device));
   std::memset(&sum, 0, sizeof(sum));
   c->iters.clear();
@@ -1027,14 +1043,15 @@ int solve(bsgpu_ctx* c, const bsgpu_options& o, bsgpu_summary& sum) {
   // the assembly of the step after this one goes out ahead of the decision (enqueue_step) where it is short — a wrong guess costs its
   // length: nothing on the reference's window sizes, C2's three guesses in ten that miss cost more than the seven that hit gain (measured)
   static const int ahead_env = getenv("BSGPU_LM_AHEAD") ? atoi(getenv("BSGPU_LM_AHEAD")) : -1;
-  const bool lm_ahead = ahead_env >= 0 ? ahead_env != 0 : (c->vis.n <= kAssemblyAheadMaxFactors && c->n_res <= kAssemblyAheadMaxResiduals);   // (pose-only windows too: their assembly takes no radius, only the guess "accepted")
+  // (a free extrinsic pair: host-decided steps — no assembly ahead, no decision on the device)
+  const bool lm_ahead = !c->calib.on && (ahead_env >= 0 ? ahead_env != 0 : (c->vis.n <= kAssemblyAheadMaxFactors && c->n_res <= kAssemblyAheadMaxResiduals));   // (pose-only windows too: their assembly takes no radius, only the guess "accepted")
   // (the radius of LmState::advance for a relative decrease above 0.937, in its own arithmetic: r / (1/3) is not 3 r in every last bit)
   // ... and only while the guesses hold: after a step that did not end "accepted, at the guessed radius" (a pose graph's early steps, C2's
   // fifth to seventh) the next assembly waits for the decision again, until a step ends that way
   // Windows above those sizes: the assembly ahead at the radius the DEVICE decides (enqueue_step, LmDecide) — no guess that can miss, and the
   // candidate's cost-only pass goes.  BSGPU_LM_DEVICE=0: never, 1: on the smaller windows too (instead of their guesses).
   static const int dev_env = getenv("BSGPU_LM_DEVICE") ? atoi(getenv("BSGPU_LM_DEVICE")) : -1;
-  const bool dev_possible = dev_env != 0 && ahead_env != 0 && c->vis.n_lm > 0 && c->d_dec != nullptr && !c->use_graphs && !c->use_pcg && !c->use_spcg;
+  const bool dev_possible = !c->calib.on && dev_env != 0 && ahead_env != 0 && c->vis.n_lm > 0 && c->d_dec != nullptr && !c->use_graphs && !c->use_pcg && !c->use_spcg;
   // (a smaller window whose last guess missed waits for the host's decision until a step ends as guessed again; the device deciding for it
   //  meanwhile measured the same — scripts/rejected_steps.py, 50 KF x 5 000 with four rejected steps in twenty: 6 700 LM it/s either way)
   const bool lm_dev = dev_possible && (dev_env > 0 || !lm_ahead);

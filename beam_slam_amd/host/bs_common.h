@@ -232,7 +232,11 @@ class Orientation3D : public fuse_variables::FixedSizeVariable<4> {
   BS_CLONE_IN_PLACE(Orientation3D)
   int manifold() const override { return BSGPU_MANIFOLD_QUAT_RIGHT; }
   size_t localSize() const override { return 3; }
-  bool holdConstant() const override { return true; }
+  bool holdConstant() const override { return hold_constant_; }
+  // online calibration: the reference switches the block free by returning false above; here the graph's owner says so before it adds it
+  void setHoldConstant(bool hold) { hold_constant_ = hold; }
+ private:
+  bool hold_constant_ = true;
 };
 class Position3D : public fuse_variables::FixedSizeVariable<3> {
  public:
@@ -243,7 +247,10 @@ class Position3D : public fuse_variables::FixedSizeVariable<3> {
   std::string type() const override { return "bs_variables::Position3D"; }
   fuse_core::Variable::SharedPtr clone() const override { return std::make_shared<Position3D>(*this); }
   BS_CLONE_IN_PLACE(Position3D)
-  bool holdConstant() const override { return true; }
+  bool holdConstant() const override { return hold_constant_; }
+  void setHoldConstant(bool hold) { hold_constant_ = hold; }   // (as Orientation3D's)
+ private:
+  bool hold_constant_ = true;
 };
 }  // namespace bs_variables
 

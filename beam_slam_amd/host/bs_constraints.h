@@ -421,6 +421,30 @@ class RelativeVec3Constraint : public fuse_core::Constraint {
 }  // namespace fuse_constraints
 
 namespace bs_constraints {
+// bs_constraints::AbsolutePose3DConstraint (global/absolute_pose_3d_constraint.cpp:12-52): the pose prior on an UNSTAMPED pair — what
+// VisualMap::AddCameraCalibration puts on the camera extrinsics (bs_models/src/lib/vision/visual_map.cpp:610-618).  Same functor and
+// packing as the stamped constraint: BSGPU_F_ABSPOSE.
+class AbsolutePose3DConstraint : public fuse_core::Constraint {
+ public:
+  AbsolutePose3DConstraint(const std::string& source, const bs_variables::Position3D& position, const bs_variables::Orientation3D& orientation,
+                           const Vector7d& mean, const Mat<6, 6>& covariance)
+      : Constraint(source, {position.uuid(), orientation.uuid()}), mean_(mean) {
+    if (!bs_math::sqrtInformationUpper(covariance, sqrt_information_)) throw std::invalid_argument("covariance is not positive definite");
+  }
+  std::string type() const override { return "bs_constraints::AbsolutePose3DConstraint"; }
+  void pack(const BlockOf& block_of, fuse_core::FactorTables& t) const override {
+    appendBlocks(*this, block_of, t.idx[BSGPU_F_ABSPOSE]);
+    auto& c = t.consts[BSGPU_F_ABSPOSE];
+    c.insert(c.end(), mean_.begin(), mean_.end());
+    appendMat(c, sqrt_information_);
+    t.pushLoss(BSGPU_F_ABSPOSE, loss());
+  }
+  SharedPtr clone() const override { return std::make_shared<AbsolutePose3DConstraint>(*this); }
+ protected:
+  Vector7d mean_;
+  Mat<6, 6> sqrt_information_;
+};
+
 // the reference's aliases (global/absolute_constraint.h:10-25, relative_pose/relative_constraints.h:12-19)
 inline fuse_core::Constraint::SharedPtr AbsoluteVelocityLinear3DStampedConstraint(const std::string& src, const fuse_variables::VelocityLinear3DStamped& v, const Vec3& mean, const Mat<3, 3>& cov) {
   return std::make_shared<fuse_constraints::AbsoluteVec3Constraint>("fuse_constraints::AbsoluteVelocityLinear3DStampedConstraint", src, v, mean, cov); }

@@ -266,8 +266,13 @@ def _perturb_quat(q, rng, sigma):
 # ---------------------------------------------------------------------------------------------
 def vio_window(n_kf=200, n_lm=50000, seed=20250620, kf_rate=10.0, imu_rate=200.0, track_min=4, track_max=12,
                pixel_sigma=1.0, w_reproj=1.0, cauchy_a=5.0, w_inertial=1.0, with_imu=True, sigma_rot=0.02,
-               sigma_pos=0.05, sigma_vel=0.05, sigma_lm=0.1, kf0=0, first_prior=True, bias_seed=None):
+               sigma_pos=0.05, sigma_vel=0.05, sigma_lm=0.1, kf0=0, first_prior=True, bias_seed=None, online_calib=False,
+               free_extrinsics=False, calib_prior_cov=1e-5):
     """SURVEY.md §8d "C2 synthetic input".  Returns a Problem; p.meta holds ground truth.
+    online_calib: every reprojection factor is an EuclideanReprojectionConstraintOnlineCalib (type 1) naming one extrinsic pair
+    (q_BASELINK_CAM, p_BASELINK_CAM), perturbed from T_IMU_CAM, with the reference's AbsolutePose3DConstraint prior of covariance
+    calib_prior_cov I on it (bs_models/src/lib/vision/visual_map.cpp:598-624); free_extrinsics: the pair is estimated with the window
+    (else held constant, as bs_variables' holdConstant() does).  The defaults leave the window as it was, value for value.
     kf0 / first_prior / bias_seed: the window starts at key frame kf0 of the (periodic) trajectory, has no prior on its first state,
     and takes the IMU biases of another seed — neighbouring submaps of one trajectory that share a boundary key frame (chain_windows)."""
     rng = np.random.default_rng(seed)
@@ -340,10 +345,25 @@ def vio_window(n_kf=200, n_lm=50000, seed=20250620, kf_rate=10.0, imu_rate=200.0
     n_obs = obs_l.size
     idx = np.stack([kf_blocks[obs_k, 0], kf_blocks[obs_k, 1], lm_blocks[obs_l], np.full(n_obs, cam, np.int32)], axis=1)
     consts = np.concatenate([uv, np.full((n_obs, 1), w_reproj)], axis=1)
+    ftype = capi.F_REPROJ
+    ext_blocks = None
+    if online_calib:
+        # (its own generator: the rest of the window is the plain window's, draw for draw)
+        rng_e = np.random.default_rng([seed, 0x0CA11B])
+        q_bc = _perturb_quat(rot_to_quat(T_IMU_CAM[:3, :3]), rng_e, 0.01)
+        p_bc = T_IMU_CAM[:3, 3] + rng_e.normal(0, 0.05, 3)
+        b_qe = pr.add_quat(q_bc, const=not free_extrinsics)
+        b_pe = pr.add_block(p_bc, const=not free_extrinsics)
+        ext_blocks = (b_qe, b_pe)
+        idx = np.concatenate([idx[:, :3], np.full((n_obs, 1), b_qe, np.int32), np.full((n_obs, 1), b_pe, np.int32), idx[:, 3:]], axis=1)
+        ftype = capi.F_REPROJ_ONLINE_CALIB
     if cauchy_a is None:
-        pr.add_factors(capi.F_REPROJ, idx, consts)
+        pr.add_factors(ftype, idx, consts)
     else:
-        pr.add_factors(capi.F_REPROJ, idx, consts, capi.LOSS_CAUCHY, cauchy_a * w_reproj)  # a = 5 w: visual_odometry_params.h:77-80
+        pr.add_factors(ftype, idx, consts, capi.LOSS_CAUCHY, cauchy_a * w_reproj)  # a = 5 w: visual_odometry_params.h:77-80
+    if online_calib:
+        A = sqrt_information_upper(calib_prior_cov * np.eye(6))
+        pr.add_factors(capi.F_ABSPOSE, [[b_pe, b_qe]], [np.concatenate([p_bc, q_bc, A.ravel()])])
     if imu_fac:
         idx = np.concatenate([kf_blocks[:-1], kf_blocks[1:]], axis=1)
         pr.add_factors(capi.F_IMU_DELTA, idx, np.stack(imu_fac))
@@ -357,6 +377,8 @@ def vio_window(n_kf=200, n_lm=50000, seed=20250620, kf_rate=10.0, imu_rate=200.0
     pr.meta = dict(kind="vio_window", n_kf=n_kf, n_lm=n_lm, n_obs=int(n_obs), n_imu=len(imu_fac), seed=seed, kf0=kf0,
                    kf_blocks=kf_blocks, lm_blocks=lm_blocks, q_true=q_true, p_true=p_true, v_true=v_true,
                    P_true=P_true, bg_true=bg_true, ba_true=ba_true)
+    if ext_blocks is not None:
+        pr.meta.update(ext_blocks=ext_blocks, cam=cam)
     return pr
 
 

@@ -92,8 +92,17 @@ enum {
    *   (visual/euclidean_reprojection_functor_online_calib.h:16-83, AutoDiff<2,4,3,3,4,3>)
    *   idx   : q_WB, t_WB, P, q_BASELINK_CAM, p_BASELINK_CAM, camera-table index (K only)
    *   consts: u, v, w
-   *   The two extrinsic blocks must be constant (bs_variables::Orientation3D /
-   *   Position3D::holdConstant() == true, bs_variables/src/orientation_3d.cpp:39-41). */
+   *   The two extrinsic blocks are constant in the reference as shipped (bs_variables::
+   *   Orientation3D / Position3D::holdConstant() == true, bs_variables/src/orientation_3d.cpp:39-41):
+   *   their values are then folded into a derived camera at bsgpu_finalize().  ONE pair per
+   *   window may be free instead (both blocks, or one of them) — online calibration: it is
+   *   estimated with the window, the landmarks still eliminated, and bsgpu_evaluate, bsgpu_solve,
+   *   the covariance queries of pose-side blocks (the pair's two included) and
+   *   bsgpu_reprojection_errors work at its current values.  Such a window is solved by LM on the
+   *   exact path.  BSGPU_ERR_UNSUPPORTED: a second free pair; such a factor on a landmark block
+   *   that is not eliminated (shared with another kind of factor), or whose pose and landmark
+   *   blocks are all constant; BSGPU_TR_DOGLEG, BSGPU_LINEAR_PCG / SCHUR_PCG; bsgpu_marginalize;
+   *   bsgpu_covariance_requests naming an eliminated landmark of such a window.               */
   BSGPU_F_REPROJ_ONLINE_CALIB = 1,
   /* bs_constraints::RelativeImuState3DStampedConstraint
    *   (inertial/normal_delta_imu_state_3d_cost_functor.h:18-141, AutoDiff<15, 4,3,3,3,3, 4,3,3,3,3>)
