@@ -114,12 +114,18 @@ SYMBOLS = [
     "evaluate", "num_residuals", "num_parameters_tangent", "tangent_offset", "covariance", "marginalize", "get_marginal",
     "reprojection_errors", "preintegrate", "triangulate", "time_reproj_jacobian_ms", "reproj_jacobian_bytes", "dense_solve", "plan_info",
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
-    "covariance_requests", "localize_frames", "num_factorizations",
+    "covariance_requests", "localize_frames", "num_factorizations", "essential_ransac",
 ]
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
 _bp = C.POINTER(C.c_uint8)
+
+#: bsgpu_essential_ransac: per-set status values, the set-size limit and the typed prototype
+RANSAC_OK, RANSAC_TOO_FEW, RANSAC_NO_MODEL = 0, 1, 2
+RANSAC_MAX_MATCHES = 65536
+ESSENTIAL_RANSAC_ARGTYPES = [C.c_void_p, C.c_int32, _ip, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int32, C.c_uint64, _bp, _dp, _ip, _ip,
+                             _ip, _ip]
 
 
 def _ptr(a, typ):

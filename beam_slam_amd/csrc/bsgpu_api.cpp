@@ -1175,6 +1175,64 @@ int bsgpu_localize_frames(bsgpu_ctx* c, int32_t n_frames, const int32_t* obs_sta
   return BSGPU_OK;
 } catch (...) { return api_exception(c); }
 
+int bsgpu_essential_ransac(bsgpu_ctx* c, int32_t n_sets, const int32_t* match_start, const double* px_prev, const double* px_cur,
+                           const double* K, double prob, double threshold_px, int32_t max_iters, uint64_t seed, uint8_t* mask, double* E,
+                           int32_t* n_inliers, int32_t* n_iters, int32_t* best_sample, int32_t* status) try {
+  if (!c) return BSGPU_ERR_INVALID;
+  if (n_sets < 0 || !match_start || !px_prev || !px_cur || !K || !mask || !status)
+    return fail(c, BSGPU_ERR_INVALID, "essential_ransac: null argument");
+  if (!(prob > 0.0 && prob < 1.0)) return fail(c, BSGPU_ERR_INVALID, "essential_ransac: prob must lie inside (0, 1)");
+  if (!(threshold_px > 0.0) || max_iters <= 0) return fail(c, BSGPU_ERR_INVALID, "essential_ransac: threshold_px and max_iters must be positive");
+  if (match_start[0] != 0) return fail(c, BSGPU_ERR_INVALID, "essential_ransac: match_start[0] must be 0");
+  for (int k = 0; k < n_sets; ++k) {
+    if (match_start[k + 1] < match_start[k]) return fail(c, BSGPU_ERR_INVALID, "essential_ransac: match_start must be non-decreasing");
+    if (!(K[4 * (size_t)k] > 0.0) || !(K[4 * (size_t)k + 1] > 0.0)) return fail(c, BSGPU_ERR_INVALID, "essential_ransac: focal lengths must be positive");
+  }
+  for (int k = 0; k < n_sets; ++k)
+    if (match_start[k + 1] - match_start[k] > BSGPU_RANSAC_MAX_MATCHES)
+      return fail(c, BSGPU_ERR_UNSUPPORTED, "essential_ransac: a set holds more than BSGPU_RANSAC_MAX_MATCHES matches");
+  if (n_sets == 0) return BSGPU_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // one device buffer: inputs [match_start | K | px_prev | px_cur], outputs [E | per-set ints | mask]
+  const size_t n_m = (size_t)match_start[n_sets];
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_start = al(sizeof(int32_t) * ((size_t)n_sets + 1)), b_K = al(sizeof(double) * 4 * (size_t)n_sets), b_px = al(sizeof(double) * 2 * n_m);
+  const size_t in_bytes = b_start + b_K + 2 * b_px;
+  const size_t out_E = al(sizeof(double) * 9 * (size_t)n_sets), out_i = al(sizeof(int32_t) * kRansacOutInts * (size_t)n_sets), out_m = al(n_m);
+  std::vector<char> h_in(in_bytes), h_out(out_E + out_i + out_m);
+  std::memcpy(h_in.data(), match_start, sizeof(int32_t) * ((size_t)n_sets + 1));
+  std::memcpy(h_in.data() + b_start, K, sizeof(double) * 4 * (size_t)n_sets);
+  if (n_m) {
+    std::memcpy(h_in.data() + b_start + b_K, px_prev, sizeof(double) * 2 * n_m);
+    std::memcpy(h_in.data() + b_start + b_K + b_px, px_cur, sizeof(double) * 2 * n_m);
+  }
+  char* d = nullptr;
+  if (hipMalloc((void**)&d, in_bytes + h_out.size()) != hipSuccess) { (void)hipGetLastError(); return fail(c, BSGPU_ERR_DEVICE, "essential_ransac: out of device memory"); }
+  hipError_t e = hipMemcpyAsync(d, h_in.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    launch_essential_ransac(c->stream, n_sets, (const int*)d, (const double2*)(d + b_start + b_K), (const double2*)(d + b_start + b_K + b_px),
+                            (const double*)(d + b_start), prob, threshold_px, max_iters, seed, (unsigned char*)(d + in_bytes + out_E + out_i),
+                            (double*)(d + in_bytes), (int*)(d + in_bytes + out_E));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d + in_bytes, h_out.size(), hipMemcpyDeviceToHost, c->stream);
+  const hipError_t e2 = hipStreamSynchronize(c->stream);
+  (void)hipFree(d);
+  if (e != hipSuccess || e2 != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "essential_ransac: device error");
+  const double* oE = (const double*)h_out.data();
+  const int32_t* oi = (const int32_t*)(h_out.data() + out_E);
+  if (n_m) std::memcpy(mask, h_out.data() + out_E + out_i, n_m);
+  if (E) std::memcpy(E, oE, sizeof(double) * 9 * (size_t)n_sets);
+  for (int k = 0; k < n_sets; ++k) {
+    const int32_t* r = oi + (size_t)kRansacOutInts * k;
+    if (n_inliers) n_inliers[k] = r[0];
+    if (n_iters) n_iters[k] = r[1];
+    if (best_sample) std::memcpy(best_sample + 5 * (size_t)k, r + 2, 5 * sizeof(int32_t));
+    status[k] = r[7];
+  }
+  return BSGPU_OK;
+} catch (...) { return api_exception(c); }
+
 double bsgpu_time_reproj_jacobian_ms(bsgpu_ctx* c, int32_t reps) {
   if (!c) return -1.0;
   if (finalize(c) != BSGPU_OK || c->vis.n == 0 || reps <= 0) return -1.0;

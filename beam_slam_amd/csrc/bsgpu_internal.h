@@ -550,6 +550,12 @@ void launch_localize(hipStream_t s, int n_frames, const int* obs_start, const do
                      const double* x, const DevCamera* cams, const int* cam_of, const double* pose_in, int loss_kind, double loss_a,
                      double sqrt_info, int truncate, int min_points, int width, int height, const bsgpu_options& opt, double* out,
                      int* out_i);
+// five-point RANSAC track screening (k_ransac.hip, bsgpu_essential_ransac): one workgroup per match set; K 4 per set (fx fy cx cy);
+// mask 1 byte per match, out_E 9 per set, out_i kRansacOutInts per set [n_inliers | n_iters | best_sample 5 | status]
+constexpr int kRansacOutInts = 8;
+void launch_essential_ransac(hipStream_t s, int n_sets, const int* match_start, const double2* px_prev, const double2* px_cur,
+                             const double* K, double prob, double threshold_px, int max_iters, uint64_t seed, unsigned char* mask,
+                             double* out_E, int* out_i);
 // device-side flattening of the reprojection factors (k_flatten.hip): 0 = done, 1 = take the host path, < 0 = device error.
 // `res` non-null: the raw table is already on the device, its block columns naming caller slots (SlotMirror, bsgpu_ctx.h)
 struct FlattenResident { const int* idx; const double* consts; const int* loss_kind; const double* loss_a; const int* slot_map; };

@@ -100,6 +100,29 @@ class GpuSolver(capi.Solver):
                      float(max_dist), float(max_reproj), pts.ctypes.data, st.ctypes.data))
         return pts, st
 
+    def essential_ransac(self, match_start, px_prev, px_cur, K, prob=0.99, threshold_px=1.0, max_iters=1000, seed=0):
+        """bsgpu_essential_ransac: cv::findEssentialMat(..., cv::RANSAC, prob, threshold_px, mask) for a batch of match sets.  Set k
+        holds matches [match_start[k], match_start[k+1]); px_prev / px_cur (n x 2) pixels; K (n_sets x 4, or 4 for all): fx fy cx cy.
+        Returns a dict of arrays: mask (n, uint8), E (S x 3 x 3), n_inliers, n_iters, best_sample (S x 5), status (S)."""
+        import numpy as np
+        ms = np.ascontiguousarray(match_start, np.int32)
+        S = ms.size - 1
+        p1 = np.ascontiguousarray(px_prev, np.float64).reshape(-1, 2)
+        p2 = np.ascontiguousarray(px_cur, np.float64).reshape(-1, 2)
+        Ks = np.ascontiguousarray(np.broadcast_to(np.asarray(K, np.float64).reshape(-1, 4), (S, 4)))
+        if p1.shape != p2.shape or (ms.size and p1.shape[0] < int(ms.max())):
+            raise capi.SolverError(capi.ERR_INVALID, "essential_ransac: match_start names more matches than were passed")
+        out = dict(mask=np.zeros(p1.shape[0], np.uint8), E=np.zeros((S, 3, 3)), n_inliers=np.zeros(S, np.int32), n_iters=np.zeros(S, np.int32),
+                   best_sample=np.zeros((S, 5), np.int32), status=np.zeros(S, np.int32))
+        fn = lib().bsgpu_essential_ransac
+        fn.argtypes = capi.ESSENTIAL_RANSAC_ARGTYPES
+        _dp, _ip, _bp = capi._dp, capi._ip, capi._bp
+        self._chk(fn(self._ctx, S, ms.ctypes.data_as(_ip), p1.ctypes.data_as(_dp), p2.ctypes.data_as(_dp), Ks.ctypes.data_as(_dp),
+                     float(prob), float(threshold_px), int(max_iters), int(seed) & ((1 << 64) - 1), out["mask"].ctypes.data_as(_bp),
+                     out["E"].ctypes.data_as(_dp), out["n_inliers"].ctypes.data_as(_ip), out["n_iters"].ctypes.data_as(_ip),
+                     out["best_sample"].ctypes.data_as(_ip), out["status"].ctypes.data_as(_ip)))
+        return out
+
     @staticmethod
     def batch_stats():
         """(windows solved by the batched launches of bsgpu_solve_batch so far in this process, rounds = sets of launches they took)."""

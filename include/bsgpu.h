@@ -527,6 +527,38 @@ int bsgpu_localize_frames(bsgpu_ctx* ctx, int32_t n_frames, const int32_t* obs_s
                           int32_t image_width, int32_t image_height, const bsgpu_options* options, double* q_out, double* p_out,
                           double* cov_out, double* avg_reproj, double* final_cost, int32_t* iterations, int32_t* status);
 
+/* Five-point RANSAC track screening for a batch of match sets — the
+ * cv::findEssentialMat(fp1, fp2, K, cv::RANSAC, prob, threshold, mask) call of VisualOdometry::AddMeasurementsToContainer
+ * (bs_models/src/visual_odometry.cpp:516-519) and SLAMInitialization (slam_initialization.cpp:898-901), whose mask decides which
+ * tracks are erased before a frame is localised.  [EXT] OpenCV is not in the reference checkout: the semantics below are RECALLED
+ * from OpenCV 4 (findEssentialMat / RANSACPointSetRegistrator) and could not be verified (DESIGN.md "Essential-matrix RANSAC").
+ *   set k holds matches [match_start[k], match_start[k+1]) (match_start[0] == 0, non-decreasing); px_prev / px_cur: 2 per match,
+ *   pixels of the previous and the current frame; K: per set (fx, fy, cx, cy).
+ *   Pixels are normalised with K, threshold_px is divided by (fx + fy) / 2.  Minimal sample: 5 matches; model: every real essential
+ *   matrix of the five-point solver; error: the squared Sampson distance; inlier: error <= threshold^2.  Loop: niters = max_iters;
+ *   for sample s = 0, 1, ... while s < niters, every solution of sample s (in ascending order of its first entry, |E|_F = 1, largest
+ *   entry positive) whose inlier count is strictly greater than max(best, 4) becomes the best and sets
+ *   niters = update(prob, (n - good) / n, 5, niters) [num = log(1 - prob), den = log(1 - (1 - ep)^5); niters when den >= 0 or
+ *   -num >= niters * -den, otherwise round(num / den); 0 when ep == 0].  No refit; the mask is the best model's inlier set.
+ *   Sampler (part of the contract, all arithmetic mod 2^64): state = seed ^ (k * 0x9E3779B97F4A7C15) ^ (s * 0xBF58476D1CE4E5B9) with
+ *   k the set's position in THIS call; each draw is splitmix64 (state += 0x9E3779B97F4A7C15; z = state;
+ *   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^= z >> 31; index = z mod n); a draw equal
+ *   to an earlier index of the same sample is drawn again.  A sample whose solver finds no real solution counts as an iteration.
+ * Outputs: mask (1 per match: 1 keep, 0 erase); E (9 per set, row-major, on normalised coordinates, may be NULL); n_inliers, n_iters
+ * (samples the loop consumed), best_sample (5 per set: the winning sample's match indices inside the set) — each may be NULL;
+ * status per set: BSGPU_RANSAC_OK; BSGPU_RANSAC_TOO_FEW (fewer than 5 matches: mask all 1 — the reference's erase loop runs over an
+ * empty mask and erases nothing — E zeros, n_iters 0, best_sample -1); BSGPU_RANSAC_NO_MODEL (no solution ever reached 5 inliers:
+ * mask all 1, E zeros; a decision of this library, OpenCV's behaviour there is not verifiable here).
+ * A set's results do not depend on the other sets of the call except through its position k.  The context need not be finalized:
+ * only its device and stream are used, and it is not changed.  INVALID: a NULL ctx / match_start / px_prev / px_cur / K / mask /
+ * status, a malformed match_start, prob outside (0, 1), threshold_px <= 0, max_iters <= 0, a focal length <= 0.  UNSUPPORTED: a set
+ * of more than BSGPU_RANSAC_MAX_MATCHES matches.                                                                                  */
+enum { BSGPU_RANSAC_OK = 0, BSGPU_RANSAC_TOO_FEW = 1, BSGPU_RANSAC_NO_MODEL = 2 };
+#define BSGPU_RANSAC_MAX_MATCHES 65536
+int bsgpu_essential_ransac(bsgpu_ctx* ctx, int32_t n_sets, const int32_t* match_start, const double* px_prev, const double* px_cur,
+                           const double* K, double prob, double threshold_px, int32_t max_iters, uint64_t seed, uint8_t* mask,
+                           double* E, int32_t* n_inliers, int32_t* n_iters, int32_t* best_sample, int32_t* status);
+
 /* ---- measurement helpers (used by bench.py only) --------------------------- */
 /* Launches the Jacobian-evaluation kernel of the reprojection factors `reps`
  * times on the context's stream between two HIP events and returns the average
