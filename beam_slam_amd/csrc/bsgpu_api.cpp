@@ -9,6 +9,7 @@
 #include <thread>
 
 #include "bsgpu_ctx.h"
+#include "bsgpu_env.h"
 
 using namespace bsg;
 
@@ -249,7 +250,7 @@ int bsgpu_sync_factors_indirect(bsgpu_ctx* c, int32_t type, int32_t n, const int
   // the previous call's asynchronous copies read the mirror's host vectors (pageable memory), which are rewritten — and may be
   // re-allocated — below: they must have left (the stream is idle between two cycles, this costs a few microseconds)
   if (m.d_idx) { HIPCHK(c, hipSetDevice(c->device)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
-  const bool force_full = getenv("BSGPU_SYNC_FULL") != nullptr, check = getenv("BSGPU_SYNC_CHECK") != nullptr;   // (debug switches, read per call: a test sets them mid-process)
+  const bool force_full = env_set("BSGPU_SYNC_FULL"), check = env_set("BSGPU_SYNC_CHECK");   // (debug switches, read per call: a test sets them mid-process)
   const bool full = n_changed < 0 || !m.valid || force_full;
   auto row_ok = [&](size_t r) {
     const int32_t* row = slot_idx + 4 * r;
@@ -309,10 +310,8 @@ int bsgpu_sync_factors_indirect(bsgpu_ctx* c, int32_t type, int32_t n, const int
   const int rc = invalidate_keep_values(c);
   if (rc != BSGPU_OK) return rc;
   // ---- device copy (what finalize() flattens from when the window is large enough for the device path)
-  {
-    const char* fe = getenv("BSGPU_FLATTEN");   // (forced device flattening — the tests — keeps the resident copy of a small window too)
-    if (n < kDeviceFlattenMin && !(fe && !strcmp(fe, "device") && n > 0)) { m.dev_valid = false; return BSGPU_OK; }
-  }
+  // (forced device flattening — the tests — keeps the resident copy of a small window too)
+  if (n < kDeviceFlattenMin && !(env_flatten_is("device") && n > 0)) { m.dev_valid = false; return BSGPU_OK; }
   HIPCHK(c, hipSetDevice(c->device));
   if ((size_t)n > m.d_cap) {
     const size_t cap = (size_t)n + (size_t)n / 4 + 4096;
@@ -406,23 +405,19 @@ int bsgpu_solve_batch(bsgpu_ctx* const* ctxs, int32_t n, const bsgpu_options* o,
   std::vector<int> rc(n, BSGPU_OK);
   // The windows the batched kernels cover (bsgpu_batch.cpp: Euclidean-landmark windows on the fused factorisation) advance together,
   // one set of launches per LM iteration; every other window gets a thread of its own on its context's stream, as before.
-  // BSGPU_BATCH_THREADS=1: the thread-per-window form for all of them.
   std::vector<int> batched, alone;
-  static const bool threads_only = getenv("BSGPU_BATCH_THREADS") != nullptr;
   for (int i = 0; i < n; ++i) {
     bool covered = false;
-    if (!threads_only) {
-      const bsgpu_options& oi = o[options_stride ? i : 0];
-      try {
-        covered = finalize(ctxs[i]) == BSGPU_OK && batch_covers(ctxs[i], oi);
-        if (covered && !batched.empty()) {   // (one device, and the options that are part of the argument tables equal)
-          const bsgpu_options& o0 = o[options_stride ? batched[0] : 0];
-          covered = ctxs[batched[0]]->device == ctxs[i]->device && o0.jacobi_scaling == oi.jacobi_scaling && o0.min_lm_diagonal == oi.min_lm_diagonal &&
-                    o0.max_lm_diagonal == oi.max_lm_diagonal;
-        }
+    const bsgpu_options& oi = o[options_stride ? i : 0];
+    try {
+      covered = finalize(ctxs[i]) == BSGPU_OK && batch_covers(ctxs[i], oi);
+      if (covered && !batched.empty()) {   // (one device, and the options that are part of the argument tables equal)
+        const bsgpu_options& o0 = o[options_stride ? batched[0] : 0];
+        covered = ctxs[batched[0]]->device == ctxs[i]->device && o0.jacobi_scaling == oi.jacobi_scaling && o0.min_lm_diagonal == oi.min_lm_diagonal &&
+                  o0.max_lm_diagonal == oi.max_lm_diagonal;
       }
-      catch (...) { covered = false; }
     }
+    catch (...) { covered = false; }
     (covered ? batched : alone).push_back(i);
   }
   if (batched.size() < 2) { alone.insert(alone.end(), batched.begin(), batched.end()); batched.clear(); }
@@ -1314,10 +1309,7 @@ int bsgpu_dense_solve(int device, int32_t n, const double* A, const double* b, d
   std::vector<uint8_t> adj((size_t)T * T, 0);
   for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) if (A[(size_t)i * n + j] != 0.0) adj[(size_t)(i / 64) * T + j / 64] = 1;
   DensePlan P;
-  {
-    const char* e3 = getenv("BSGPU_SHARED");
-    P.build(n, adj, std::max(1, (int)max_chains), 1, !(e3 && atoi(e3) == 0));
-  }
+  P.build(n, adj, std::max(1, (int)max_chains), 1, env_shared());
   const int npad = P.npad;
   std::vector<double> hS((size_t)npad * npad, 0.0);
   for (int i = 0; i < n; ++i) for (int j = 0; j < n; ++j) hS[(size_t)P.spos(i) * npad + P.spos(j)] = A[(size_t)i * n + j];
@@ -1331,8 +1323,7 @@ int bsgpu_dense_solve(int device, int32_t n, const double* A, const double* b, d
   int *dpot2 = nullptr, *dcb = nullptr, *dce = nullptr, *dsync = nullptr, *dfsync = nullptr, *dtot = nullptr;
   double* dW = nullptr;
   FusedTask* dft = nullptr;
-  const char* ef = getenv("BSGPU_CHOL_FUSED");
-  const bool fused = !(ef && atoi(ef) == 0) && !P.ftasks.empty();
+  const bool fused = env_chol_fused() && !P.ftasks.empty();
   hipStream_t s;
   if (hipStreamCreate(&s) != hipSuccess) return BSGPU_ERR_DEVICE;
   auto up = [](const void* src, size_t bytes, void** dst) {
@@ -1364,7 +1355,7 @@ int bsgpu_dense_solve(int device, int32_t n, const double* A, const double* b, d
     (void)hipEventRecord(e0, s);
     DenseDev D{dnreal, drows, dpan, dLp, dV, dpot2, dcb, dce, dsync, dft, dfsync};
     D.Winv = dW; D.tile_tot = dtot;
-    if (P.bs_level_sync && !getenv("BSGPU_BACKSOLVE_LEGACY") &&
+    if (P.bs_level_sync && !env_backsolve_legacy() &&
         up(P.bs_desc_chain.data(), sizeof(int) * P.bs_desc_chain.size(), (void**)&dbc) && up(P.rows_flat_chain.data(), sizeof(int) * P.rows_flat_chain.size(), (void**)&drc) &&
         up(P.bs_upd.data(), sizeof(int) * P.bs_upd.size(), (void**)&dbu) && up(P.bs_upd_rows.data(), sizeof(int) * P.bs_upd_rows.size(), (void**)&dbur)) {
       D.bs_desc_chain = dbc; D.rows_flat_chain = drc; D.bs_upd = dbu; D.bs_upd_rows = dbur;

@@ -27,16 +27,11 @@
 #include <thread>
 
 #include "bsgpu_ctx.h"
+#include "bsgpu_env.h"
 #include "lm_state.h"
 
 namespace bsg {
 namespace {
-
-// the environment switches that change which launches a lone step is made of (the batch mirrors the default set only): read once
-bool env_step_variants() {
-  static const bool v = getenv("BSGPU_EVAL_MERGE") || getenv("BSGPU_SCALARS_EVENT") || getenv("BSGPU_UPDATE_SEPARATE") || getenv("BSGPU_CLEAR_AT_START");
-  return v;
-}
 
 // which launches a window's step is made of — bsgpu_solve.cpp eval_all() / assemble() / linear_solve_and_candidate(), decided once
 struct WinShape {
@@ -82,7 +77,9 @@ bool batch_covers(bsgpu_ctx* c, const bsgpu_options& o) {
   } else if (!c->upd_in_mcc) return false;
   if (!c->d_ftasks || !c->d_fsync || !c->d_tile_tot || !c->d_Winv) return false;
   if (c->plan.ftasks.size() > 65535) return false;   // (the window's tasks are the y dimension of the batched factorisation's grid)
-  if (env_step_variants()) return false;
+  // the environment switches that change which launches a lone step is made of (the batch mirrors the default set only): read once
+  static const bool step_variants = env_step_variants();
+  if (step_variants) return false;
   WinShape w;
   if (!shape_of(c, w)) return false;
   // the pose-only groups that ride in no other launch must fit ONE set each (assembly one workgroup per factor; model-cost terms)
@@ -208,8 +205,7 @@ bool build_plan(BatchPlan& P, bsgpu_ctx* const* ctxs, int n, const bsgpu_options
   P.shape.resize(n);
   size_t tasks_per_round = 0, vis_factors = 0;
   for (int w = 0; w < n; ++w) tasks_per_round += ctxs[w]->plan.ftasks.size();
-  static const char* bulk_env = getenv("BSGPU_BATCH_BULK");   // (0: never, 1: always)
-  const bool bulk_lists = bulk_env ? atoi(bulk_env) != 0 : tasks_per_round >= 2048;
+  const bool bulk_lists = tasks_per_round >= 2048;
   for (int w = 0; w < n; ++w) {
     bsgpu_ctx* c = ctxs[w];
     P.ctxs.push_back(c); P.gens.push_back(c->finalize_gen); P.xptr.push_back(c->d_x);
@@ -294,8 +290,8 @@ bool build_plan(BatchPlan& P, bsgpu_ctx* const* ctxs, int n, const bsgpu_options
     int ntl = bulk ? c->n_ftasks_bulk : plain ? c->n_ftasks_plain : (int)c->plan.ftasks.size();
     const int* tt = bulk ? c->d_tile_tot_bulk : plain ? c->d_tile_tot_plain : D.tile_tot;
     // ... and, where that list is the one the row segments were made from, the list with the segments: an update task is ~7 us of a compute unit for
-    // 1.3 - 2 us of products, a segment's further updates ~2 (dense_plan.h build_row_segments; launches without turns only; BSGPU_CHOL_ROWS=0: never)
-    static const bool rows_off = (getenv("BSGPU_CHOL_ROWS") && atoi(getenv("BSGPU_CHOL_ROWS")) == 0) || (getenv("BSGPU_CHOL_NOTURN") && atoi(getenv("BSGPU_CHOL_NOTURN")) == 0);
+    // 1.3 - 2 us of products, a segment's further updates ~2 (dense_plan.h build_row_segments; launches without turns only: not under BSGPU_CHOL_NOTURN=0)
+    static const bool rows_off = env_chol_turns();
     const int src_now = bulk ? 2 : plain ? 1 : 0;
     if (bulk_lists && !rows_off && c->d_ftasks_rows && c->plan.frows_src == src_now) { tl = c->d_ftasks_rows; ntl = c->n_ftasks_rows; }
     batchargs_chol_fused(P.t_chol, c->d_S, D.Lp, c->plan.npad, tl, ntl, tt, D.nreal, D.Vinv, c->d_scal, D.fsync, D.Winv, D.rhs_rows, LmDiag(), GradNormRide(), /*diag_tasks_in_list=*/!bulk && !plain && c->plan.diag_tasks);
@@ -334,12 +330,8 @@ bool build_plan(BatchPlan& P, bsgpu_ctx* const* ctxs, int n, const bsgpu_options
     if (hipMemcpy(d, t->host.data(), t->host.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); return false; }
     t->dev = d;
   }
-  {
-    // (BSGPU_BATCH_ONE_PASS=0|1 forces it; by itself: from a million reprojection factors per round on — eight C2 windows 3.2 M, thirty-two windows of
-    //  the reference's size 0.13 M)
-    static const int env = getenv("BSGPU_BATCH_ONE_PASS") ? atoi(getenv("BSGPU_BATCH_ONE_PASS")) : -1;
-    P.one_pass = env >= 0 ? env != 0 : vis_factors >= 1000000;
-  }
+  // (from a million reprojection factors per round on — eight C2 windows 3.2 M, thirty-two windows of the reference's size 0.13 M)
+  P.one_pass = vis_factors >= 1000000;
   return true;
 }
 

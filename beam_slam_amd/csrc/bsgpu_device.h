@@ -259,7 +259,7 @@ BSG_DEV void final_reduce_done(const ReduceRide& R, int n_units, bool decided = 
     if (host_scal) __hip_atomic_store(&host_scal[SC_SEQ], R.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
-// a wave of an assembly ahead waits for the decision of the reduction riding in its launch (copy `wave & 63`): the radius, or 0 when the
+// a wave of an assembly ahead waits for the decision of the reduction riding in its launch (copy `bsg_bx & 255`): the radius, or 0 when the
 // step was not accepted (or nothing came: bounded by the wall clock)
 BSG_DEV double wait_decision(const double* dec, int copy) {
   const double* w = dec + (size_t)(copy & (kDecSlots - 1)) * kDecStride;

@@ -3,14 +3,14 @@
 #include <atomic>
 
 #include "bsgpu_ctx.h"
+#include "bsgpu_env.h"
 #include "band_plan.h"
 #include "dim_order.h"
 
 namespace bsg {
 
 int band_part_forced() {
-  const char* e = getenv("BSGPU_BAND_PART");   // (read at every finalize: tests/test_gpu_band.py changes it between solves)
-  return e ? atoi(e) : 0;
+  return env_int("BSGPU_BAND_PART", 0);   // (read at every finalize: tests/test_gpu_band.py changes it between solves)
 }
 
 namespace {
@@ -32,7 +32,7 @@ void eigen_quat_to_rot(const double* q, double* R) {
 // ---------------------------------------------------------------------------------------------------
 int finalize(bsgpu_ctx* c) {
   if (c->finalized) return BSGPU_OK;
-  const bool timing = getenv("BSGPU_TIMING") != nullptr;
+  const bool timing = env_timing();
   auto t_prev = std::chrono::steady_clock::now();
   auto lap = [&](const char* what) {
     if (!timing) return;
@@ -96,7 +96,7 @@ int finalize(bsgpu_ctx* c) {
   if (c->is_const_in.size() != (size_t)nb) c->is_const_in = c->is_const;
   for (int b = 0; b < nb; ++b) c->is_const[b] = (c->is_const_in[b] || lm_use[b] + other_use[b] == 0) ? 1 : 0;
   c->tsize.assign(nb, 0); c->toff.assign(nb, -1); c->is_lm.assign(nb, 0);
-  const bool idp_elim = !(getenv("BSGPU_IDP_ELIM") && atoi(getenv("BSGPU_IDP_ELIM")) == 0);
+  const bool idp_elim = env_idp_elim();
   for (int b = 0; b < nb; ++b) {
     if (c->size[b] > 4 || c->size[b] == 0) return fail(c, BSGPU_ERR_UNSUPPORTED, "block sizes 1..4 only");
     if (c->manifold[b] == BSGPU_MANIFOLD_QUAT_RIGHT && c->size[b] != 4) return fail(c, BSGPU_ERR_INVALID, "quaternion block must have size 4");
@@ -123,7 +123,7 @@ int finalize(bsgpu_ctx* c) {
   c->n_tan = to; c->n_lm = nl; c->n_idp_lm = n_rho;
   // every binary inverse-depth factor has an eliminated landmark: the factors' own pose-pose terms are assembled with the elimination
   // (idp_pairs_kernel) and the group leaves the generic pose-only assembly.  The unary factor's Jacobian is identically zero.
-  bool idp_direct = n_rho > 0 && !getenv("BSGPU_IDP_GENERIC_ASSEMBLY");
+  bool idp_direct = n_rho > 0 && !env_set("BSGPU_IDP_GENERIC_ASSEMBLY");
   {
     const HostGroup& g = c->groups[BSGPU_F_IDP_REPROJ];
     const int ni = kTypes[BSGPU_F_IDP_REPROJ].nidx;
@@ -151,7 +151,8 @@ int finalize(bsgpu_ctx* c) {
   }
   // (pose-only graphs above kDenseLimit go to the block-sparse PCG unless the exact factorisation is asked for — BSGPU_EXACT_POSE_GRAPH=1 at
   // finalize(): the dense tile storage, 2 x npad^2 doubles, is not allocated on spec; C4 that way: DESIGN.md 3.3)
-  const bool exact_pose_graph = getenv("BSGPU_EXACT_POSE_GRAPH") != nullptr && atoi(getenv("BSGPU_EXACT_POSE_GRAPH")) != 0;   // (forced: whatever the plan costs)
+  const int exact_env = env_exact_pose_graph();
+  const bool exact_pose_graph = exact_env > 0;   // (forced: whatever the plan costs)
   c->dense_ok = (size_t)c->npad <= kDenseLimit || ((nl + n_rho > 0 || c->n_leaf_tiles > 0 || exact_pose_graph) && (size_t)c->npad <= kDenseLimitLandmarks);   // else: block-sparse PCG (pose-only problems)
   // A pose graph above kDenseLimit whose loop closures are LOCAL (a mapper's: poses near each other) dissects into many small supernodes,
   // and its exact step — the reference's own call, SPARSE_NORMAL_CHOLESKY, submap_pose_graph_optimization.cpp:144-146 — is then cheaper
@@ -159,7 +160,7 @@ int finalize(bsgpu_ctx* c) {
   // has been found: the window is taken as dense provisionally, and goes back to the PCG below if the plan says otherwise.
   // BSGPU_EXACT_POSE_GRAPH=0 keeps every such graph on the PCG.
   const bool dense_on_trial = !c->dense_ok && nl + n_rho == 0 && (size_t)c->npad <= kDenseLimitLandmarks && c->marginals.empty() &&
-                              !(getenv("BSGPU_EXACT_POSE_GRAPH") && atoi(getenv("BSGPU_EXACT_POSE_GRAPH")) == 0);
+                              exact_env != 0;
   if (dense_on_trial) c->dense_ok = true;
   // The graph of the reduced system's tangent BLOCKS (which pairs of pose-side blocks some factor, some shared landmark or a dense prior
   // couples): what the per-dimension ordering of the factorisation is found on (dim_order.h).  A bit matrix; every place below that marks
@@ -176,10 +177,9 @@ int finalize(bsgpu_ctx* c) {
     }
   } bg;
   {
-    const char* ed = getenv("BSGPU_DIM_ORDER");
     int nbk = 0;
     for (int b = 0; b < nb; ++b) if (c->toff[b] >= 0 && c->toff[b] < c->n_pose) ++nbk;
-    if (c->dense_ok && c->n_leaf_tiles == 0 && nbk > 0 && nbk <= 16384 && !(ed && atoi(ed) == 0)) {
+    if (c->dense_ok && c->n_leaf_tiles == 0 && nbk > 0 && nbk <= 16384 && !env_zero("BSGPU_DIM_ORDER")) {
       bg.nbk = nbk; bg.words = (nbk + 63) / 64;
       bg.bid_of_t.assign(c->n_pose, -1);
       bg.t0.reserve(nbk); bg.w.reserve(nbk);
@@ -245,12 +245,12 @@ int finalize(bsgpu_ctx* c) {
   // first camera pose's landmarks, and a window of the reference's own size has too few of them per pose to fill the device (measured,
   // LM it/s band / entries: 20 KF x 500 8 410 / 8 850, 50 x 5 000 6 390 / 6 500, 100 x 20 000 4 720 / 4 690, 200 x 50 000 3 310 / 3 140).
   // BSGPU_PAIRS_BAND=0: every pair by entries (the cross-check), =1: band landmarks whatever the size (tests).
-  const char* band_env = getenv("BSGPU_PAIRS_BAND");
+  const char* band_env = env_str("BSGPU_PAIRS_BAND");
   const int n_reproj = c->groups[BSGPU_F_REPROJ].n + c->groups[BSGPU_F_REPROJ_ONLINE_CALIB].n;
   // (band_available(): the kernel's ~147 KB of dynamic LDS per workgroup, asked of this device once — a device or partition without it keeps the pair entries)
   // (a free extrinsic pair: the border kernels read the C rows and the full pose part, which only the pair-entry form keeps — k_calib.hip)
   const bool band_on = !has_calib && (band_env ? strcmp(band_env, "0") != 0 : n_reproj >= kBandMinFactors) && band_available();
-  const bool sort_entries = getenv("BSGPU_PAIR_ENTRIES_SORT") != nullptr;   // (tests: the path windows of more than 2 896 camera poses take)
+  const bool sort_entries = env_set("BSGPU_PAIR_ENTRIES_SORT");   // (tests: the path windows of more than 2 896 camera poses take)
   // ---- visual factors: camera-pose ids, factors sorted by landmark, pair entries, tile adjacency.
   // Large plain windows are flattened on the device (k_flatten.hip); everything else — and any window the device
   // path declines (online calibration, landmark blocks shared with other factors, more than 8 distinct losses, an
@@ -514,8 +514,7 @@ int finalize(bsgpu_ctx* c) {
   };
   bool flattened_on_device = false;
   {
-    const char* fe = getenv("BSGPU_FLATTEN");
-    const bool force_dev = fe && !strcmp(fe, "device"), force_host = fe && !strcmp(fe, "host");
+    const bool force_dev = env_flatten_is("device"), force_host = env_flatten_is("host");
     const HostGroup& g0 = c->groups[BSGPU_F_REPROJ];
     SlotMirror& mir = c->mirror0;
     const bool resident = mir.active && !mir.materialized && mir.dev_valid;
@@ -573,12 +572,10 @@ int finalize(bsgpu_ctx* c) {
       if (!c->calib.E || !c->calib.Et || !c->calib.part) return fail(c, BSGPU_ERR_DEVICE, "out of device memory (extrinsic border tables)");
     }
     // (bsgpu_internal.h Visual::no_cr: every factor belongs to a band landmark)
-    const char* no_cr_env = getenv("BSGPU_NO_CR");
-    V.no_cr = !(no_cr_env && atoi(no_cr_env) == 0) && V.n_band_units > 0 && V.n_seg == 0 && V.n_ent == 0 && V.n == V.n_elim && V.band_lm_id != nullptr && V.Linv && V.z;
+    V.no_cr = !env_zero("BSGPU_NO_CR") && V.n_band_units > 0 && V.n_seg == 0 && V.n_ent == 0 && V.n == V.n_elim && V.band_lm_id != nullptr && V.Linv && V.z;
     // (Visual::ja: the windows without C rows keep no translation columns in the pose part either — no factor of a constant landmark, and every reader of
     //  the layout has the B rows at hand.  J above stays sized for the full layout, JB in its place behind it: the choice needs the tables it is made from.)
-    const char* compact_env = getenv("BSGPU_COMPACT_J");
-    V.ja = V.no_cr && !(compact_env && atoi(compact_env) == 0) ? kJACompact : kJAStride;
+    V.ja = V.no_cr && !env_zero("BSGPU_COMPACT_J") ? kJACompact : kJAStride;
   }
   lap("visual upload + alloc");
   // ---- pose-only groups
@@ -690,7 +687,7 @@ int finalize(bsgpu_ctx* c) {
       std::vector<uint8_t> grouped(sg.n, 0);
       bool any_group = false;
       constexpr int kGroupMin = 4;
-      if (sg.w_last == 3 && nv * 3 <= 18 && sg.m <= 6 && (sg.m * nv * 3) % 2 == 0 && sg.n >= 64 && !getenv("BSGPU_NO_GROUP_ASSEMBLY")) {
+      if (sg.w_last == 3 && nv * 3 <= 18 && sg.m <= 6 && (sg.m * nv * 3) % 2 == 0 && sg.n >= 64 && !env_set("BSGPU_NO_GROUP_ASSEMBLY")) {
         std::vector<int> order;
         order.reserve(sg.n);
         for (int f = 0; f < sg.n; ++f) if (c->h_small_active[t][f]) order.push_back(f);
@@ -990,19 +987,17 @@ int finalize(bsgpu_ctx* c) {
   }
   // ---- tiled Cholesky plan: nested-dissection tile order, symbolic factorisation, step schedule
   {
-    const char* e = getenv("BSGPU_CHAINS");
-    const int max_chains = e ? std::max(1, atoi(e)) : 16;
+    const int max_chains = std::max(1, env_int("BSGPU_CHAINS", 16));
     {
       const int T0 = (c->n_pose + 63) / 64;
       if (c->tile_adj.size() != (size_t)T0 * T0) c->tile_adj.assign((size_t)T0 * T0, 0);
     }
-    const char* e3 = getenv("BSGPU_SHARED");   // panels of one step may update the same tiles (atomics): on unless BSGPU_SHARED=0
-    { const char* ex = getenv("BSGPU_CHOL_EXT"); c->plan.allow_ext = !(ex && atoi(ex) == 0); }
-    { const char* sp = getenv("BSGPU_CHOL_SPLIT"); if (sp) c->plan.split_depth = std::max(0, std::min(64, atoi(sp))); }   // (dense_plan.h kFusedSplit; default 2)
+    const bool shared_updates = env_shared();   // panels of one step may update the same tiles (atomics): on unless BSGPU_SHARED=0
+    c->plan.allow_ext = !env_zero("BSGPU_CHOL_EXT");
     // (the LM diagonal and the gradient norms as tasks of the factorisation's launch; BSGPU_POSE_DIAG_LAUNCH=1: their own launch, as before)
-    c->plan.diag_tasks = getenv("BSGPU_POSE_DIAG_LAUNCH") == nullptr;
+    c->plan.diag_tasks = !env_set("BSGPU_POSE_DIAG_LAUNCH");
     c->plan.rider_tasks = c->plan.diag_tasks ? (c->nb + 255) / 256 : 0;   // (0: every tile's panel has its own update tasks, also a separator's appendix tile)
-    const bool use_leaf = c->n_leaf_tiles > 0 && !getenv("BSGPU_NO_LEAF_TILES");
+    const bool use_leaf = c->n_leaf_tiles > 0 && !env_set("BSGPU_NO_LEAF_TILES");
     bool ordered = false;
     lap("blocks");
     if (bg.nbk && max_chains > 1) {
@@ -1018,31 +1013,23 @@ int finalize(bsgpu_ctx* c) {
         }
         ord.adj_ptr[a + 1] = (int)ord.adj.size();
       }
-      if (const char* ev = getenv("BSGPU_DIM_ORDER_DEPTH")) ord.max_depth = std::max(0, atoi(ev));
-      if (const char* ev = getenv("BSGPU_DIM_ABSORB")) ord.absorb = atoi(ev) != 0;   // (0: no separator joins its parent — dim_order.h absorb_separators())
-      if (const char* ev = getenv("BSGPU_DIM_T_STEP3")) ord.t_step3 = atof(ev);
-      if (const char* ev = getenv("BSGPU_DIM_MERGE")) ord.merge_dims = atoi(ev);
+      if (const char* ev = env_str("BSGPU_DIM_ORDER_DEPTH")) ord.max_depth = std::max(0, atoi(ev));
+      if (const char* ev = env_str("BSGPU_DIM_ABSORB")) ord.absorb = atoi(ev) != 0;   // (0: no separator joins its parent — dim_order.h absorb_separators())
       lap("  order: adjacency lists");
       // The dissection's cost model (chain start, hand-over, a second full tile's hand-over) is a heuristic and no one setting is best at every
       // size: (5, 10, 4) gives C2 and C3 their shortest factorisations, (2, 8, 8) / (3, 9, 8) cut a window of the reference's size into seven
-      // supernodes instead of five and are 4 % faster there and 3 - 5 % slower on C2 / C3 (scripts/ab_dim_model.sh).  What ranks the candidates
+      // supernodes instead of five and are 4 % faster there and 3 - 5 % slower on C2 / C3.  What ranks the candidates
       // right every time is the ticket order's own replay of the finished task list (DensePlan::est_makespan_us): small systems — where planning is
-      // tens of microseconds — are planned under each setting and keep the shortest replay.  BSGPU_DIM_T_CHAIN0 / _T_HOP / _T_HOP_TILE: one setting.
+      // tens of microseconds — are planned under each setting and keep the shortest replay.
       struct OrdModel { double chain0, hop, hop_tile, step3; int merge, depth; };
       std::vector<OrdModel> models = {{ord.t_chain0, ord.t_hop, ord.t_hop_tile, ord.t_step3, ord.merge_dims, ord.max_depth}};
-      {
-        const char* e0 = getenv("BSGPU_DIM_T_CHAIN0"); const char* e1 = getenv("BSGPU_DIM_T_HOP"); const char* e2 = getenv("BSGPU_DIM_T_HOP_TILE");
-        static const bool cand_off = getenv("BSGPU_DIM_CANDIDATES") && atoi(getenv("BSGPU_DIM_CANDIDATES")) == 0;
-        if (e0 || e1 || e2 || getenv("BSGPU_DIM_T_STEP3") || getenv("BSGPU_DIM_MERGE"))
-          models[0] = {e0 ? atof(e0) : ord.t_chain0, e1 ? atof(e1) : ord.t_hop, e2 ? atof(e2) : ord.t_hop_tile, ord.t_step3, ord.merge_dims, ord.max_depth};
-        else if (!cand_off && !dense_on_trial && c->n_pose <= 2000 && c->plan_pref == BSGPU_PLAN_LATENCY) {
-          // ((2, 10, 12; three-tile steps at 3.0, separators up to 40 dimensions joining their parents): what an offline search of 1 440 settings by the
-          //  replay found for C3 — 105.2 -> 102.8 us replayed, 97 -> 91.5 us measured, C3 5 875 -> 6 075 LM it/s)
-          // ((5, 40, 0; 3.0, 40; two levels deeper): the same search on pose graphs of 200 poses — 400 loop closures 256 -> 228 us replayed, 2 590 -> 3 090 LM it/s; 300: 240 -> 208 us,
-          //  18 % fewer tasks, 3 156 -> 3 535 LM it/s)
-          models.push_back({2.0, 8.0, 8.0, ord.t_step3, ord.merge_dims, ord.max_depth}); models.push_back({3.0, 9.0, 8.0, ord.t_step3, ord.merge_dims, ord.max_depth});
-          models.push_back({2.0, 10.0, 12.0, 3.0, 40, ord.max_depth}); models.push_back({5.0, 40.0, 0.0, 3.0, 40, ord.max_depth + 2});
-        }
+      if (!dense_on_trial && c->n_pose <= 2000 && c->plan_pref == BSGPU_PLAN_LATENCY) {
+        // ((2, 10, 12; three-tile steps at 3.0, separators up to 40 dimensions joining their parents): what an offline search of 1 440 settings by the
+        //  replay found for C3 — 105.2 -> 102.8 us replayed, 97 -> 91.5 us measured, C3 5 875 -> 6 075 LM it/s)
+        // ((5, 40, 0; 3.0, 40; two levels deeper): the same search on pose graphs of 200 poses — 400 loop closures 256 -> 228 us replayed, 2 590 -> 3 090 LM it/s; 300: 240 -> 208 us,
+        //  18 % fewer tasks, 3 156 -> 3 535 LM it/s)
+        models.push_back({2.0, 8.0, 8.0, ord.t_step3, ord.merge_dims, ord.max_depth}); models.push_back({3.0, 9.0, 8.0, ord.t_step3, ord.merge_dims, ord.max_depth});
+        models.push_back({2.0, 10.0, 12.0, 3.0, 40, ord.max_depth}); models.push_back({5.0, 40.0, 0.0, 3.0, 40, ord.max_depth + 2});
       }
       const bool compare = models.size() > 1;
       if (compare && c->dim_model >= 0 && c->dim_model < (int)models.size() && c->dim_model_npose == c->n_pose && c->dim_model_age < 32) {
@@ -1075,7 +1062,7 @@ int finalize(bsgpu_ctx* c) {
       }
       if (models.size() > 1) {   // (small systems, never on trial: plan, replay, keep the shortest)
         DensePlan cand = plan_base;
-        cand.build_ordered(c->n_pose, To, ord.dpos, ord.nreal, adjS, ord.piece_ranges, ord.sep_ranges_by_level, !(e3 && atoi(e3) == 0));
+        cand.build_ordered(c->n_pose, To, ord.dpos, ord.nreal, adjS, ord.piece_ranges, ord.sep_ranges_by_level, shared_updates);
         if (timing) fprintf(stderr, "[bsgpu finalize]   cost model (%.1f, %.1f, %.1f; %.1f, %d, %d): %d supernodes, depth %d, task list replayed %.1f us\n", models[mi].chain0, models[mi].hop,
                             models[mi].hop_tile, models[mi].step3, models[mi].merge, models[mi].depth, ord.n_nodes, ord.depth, cand.est_makespan_us);
         if (cand.est_makespan_us < best_span) { best_span = cand.est_makespan_us; best_plan = std::move(cand); best_ord = ord; c->dim_model = (int)mi; c->dim_model_age = 0; c->dim_model_npose = c->n_pose; }
@@ -1112,7 +1099,7 @@ int finalize(bsgpu_ctx* c) {
         }
       }
       if (keep) {
-        c->plan.build_ordered(c->n_pose, To, ord.dpos, ord.nreal, adjS, ord.piece_ranges, ord.sep_ranges_by_level, !(e3 && atoi(e3) == 0));
+        c->plan.build_ordered(c->n_pose, To, ord.dpos, ord.nreal, adjS, ord.piece_ranges, ord.sep_ranges_by_level, shared_updates);
         ordered = true;
         // (the exact step must beat a PCG solve of a few milliseconds: the critical path of the chains, and the flops at the ~3 TFLOP/s the
         // update tasks of a large plan sustain)
@@ -1131,7 +1118,7 @@ int finalize(bsgpu_ctx* c) {
     if (dense_on_trial && !ordered) c->dense_ok = false;
     if (!c->dense_ok) c->plan.build_skeleton(c->n_pose);
     else if (!ordered)
-      c->plan.build(c->n_pose, c->tile_adj, c->dense_ok ? max_chains : 1, 1, !(e3 && atoi(e3) == 0), use_leaf ? &c->leaf_tile : nullptr);
+      c->plan.build(c->n_pose, c->tile_adj, c->dense_ok ? max_chains : 1, 1, shared_updates, use_leaf ? &c->leaf_tile : nullptr);
     c->npad = c->plan.npad;
     const int T = c->plan.T;
     if (timing) fprintf(stderr, "[bsgpu finalize] task list replayed: %.1f us\n", c->plan.est_makespan_us);
@@ -1144,7 +1131,7 @@ int finalize(bsgpu_ctx* c) {
     c->d_bs_desc_chain = c->d_rows_flat_chain = c->d_bs_upd = c->d_bs_upd_rows = nullptr;
     c->d_Winv = nullptr;
     c->d_bs_chain_group = c->d_bs_grp_nchains = c->d_bs_grp_nitems = c->d_bs_items4 = c->d_bs_tile_updated = c->d_bs_sync = c->d_bs_order = nullptr;
-    if (c->plan.bs_level_sync && !getenv("BSGPU_BACKSOLVE_LEGACY")) {
+    if (c->plan.bs_level_sync && !env_backsolve_legacy()) {
       c->d_bs_desc_chain = c->upload(c->plan.bs_desc_chain); c->d_rows_flat_chain = c->upload(c->plan.rows_flat_chain);
       c->d_bs_upd = c->upload(c->plan.bs_upd); c->d_bs_upd_rows = c->upload(c->plan.bs_upd_rows);
       c->d_bs_chain_group = c->upload(c->plan.bs_chain_group); c->d_bs_grp_nchains = c->upload(c->plan.bs_grp_nchains);
@@ -1156,7 +1143,6 @@ int finalize(bsgpu_ctx* c) {
     c->d_tile_sync = c->upload(c->plan.tile_sync);
     {
       // fused single-launch factorisation (default; BSGPU_CHOL_FUSED=0 keeps the launch-per-step path): task list + zeroed counters
-      const char* ef = getenv("BSGPU_CHOL_FUSED");
       c->d_ftasks = nullptr; c->d_fsync = nullptr; c->d_tile_tot = nullptr;
       c->d_ftasks_plain = nullptr; c->d_tile_tot_plain = nullptr; c->n_ftasks_plain = 0;
       c->d_ftasks_bulk = nullptr; c->d_tile_tot_bulk = nullptr; c->n_ftasks_bulk = 0;
@@ -1164,7 +1150,7 @@ int finalize(bsgpu_ctx* c) {
       // (one workgroup of 512 threads per task, and a grid holds fewer than 2^32 threads: above 8.38 M tasks — a DENSE system of more than
       // ~23 600 dimensions, which only the exact option on a pose graph produces — the launch is refused by the runtime, so the
       // launch-per-step path runs there; scripts/c4_exact.py)
-      if (!(ef && atoi(ef) == 0) && !c->plan.ftasks.empty() && c->plan.ftasks.size() * 512 < ((size_t)1 << 32)) {
+      if (env_chol_fused() && !c->plan.ftasks.empty() && c->plan.ftasks.size() * 512 < ((size_t)1 << 32)) {
         c->d_ftasks = c->upload(c->plan.ftasks);
         c->d_tile_tot = c->upload(c->plan.tile_tot);
         if (!c->plan.ftasks_plain.empty()) {
@@ -1221,14 +1207,14 @@ int finalize(bsgpu_ctx* c) {
   chol_prepare();
   // hipGraph replay of the LM step is opt-in (BSGPU_GRAPH=1): on ROCm 7.2 the replay inserts a ~0.9 ms bubble
   // inside the long dependent kernel chain (profiles/README.md), which cancels what it saves on launches
-  c->use_graphs = getenv("BSGPU_GRAPH") != nullptr && !c->calib.on;   // (a free extrinsic pair: host-decided eager steps)
+  c->use_graphs = env_set("BSGPU_GRAPH") && !c->calib.on;   // (a free extrinsic pair: host-decided eager steps)
   HIPCHK(c, hipMemset(c->d_scal, 0, sizeof(double) * SC_NUM));
   HIPCHK(c, hipMemset(c->d_delta, 0, sizeof(double) * std::max(1, c->n_tan)));
   lap("blocks + dense buffers");
   {
     c->n_part_upd = (nb + 255) / 256;
     c->n_upd_blocks = 0; c->d_upd_blocks = nullptr; c->d_lm_xoff = nullptr;
-    if (c->vis.n_lm > 0 && !getenv("BSGPU_UPDATE_SEPARATE") && !c->calib.on) {   // (a free extrinsic pair: its back-substitution carries no riders, k_calib.hip)
+    if (c->vis.n_lm > 0 && !env_update_separate() && !c->calib.on) {   // (a free extrinsic pair: its back-substitution carries no riders, k_calib.hip)
       // the candidate update rides in the landmark back-substitution (k_reproj.hip: backsub_mcc_kernel): the eliminated Euclidean landmarks
       // are updated by the lanes that compute their step, every other block by extra workgroups of that launch
       std::vector<int> others, lm_xoff(c->vis.n_lm, 0);
@@ -1243,7 +1229,7 @@ int finalize(bsgpu_ctx* c) {
       }
     }
     c->pre_cleared = false;
-    c->upd_in_mcc = c->n_upd_blocks == 0 && c->vis.n_lm == 0 && !getenv("BSGPU_UPDATE_SEPARATE");
+    c->upd_in_mcc = c->n_upd_blocks == 0 && c->vis.n_lm == 0 && !env_update_separate();
     if (c->upd_in_mcc) c->n_part_upd = (nb + 127) / 128;
     c->d_part_upd = c->alloc<double>(2 * (size_t)c->n_part_upd + 2);
     std::vector<ReduceEntry> tab;
@@ -1408,7 +1394,7 @@ int build_bsr(bsgpu_ctx* c) {
   // ---- the solve as one persistent launch (k_pcg.hip pcg_persistent_kernel): contiguous ranges of block rows per workgroup, cut at
   // even rows (a 6x6 preconditioner block stays in one workgroup) and balanced by non-zero blocks; the columns each range names
   c->pcg_persist = PcgPersistDev();
-  if (!getenv("BSGPU_PCG_LAUNCHES") && nbr >= 64) {
+  if (!env_set("BSGPU_PCG_LAUNCHES") && nbr >= 64) {
     int n_cu = 256;
     { hipDeviceProp_t pr; if (hipGetDeviceProperties(&pr, c->device) == hipSuccess && pr.multiProcessorCount > 0) n_cu = pr.multiProcessorCount; }
     const int G = std::max(1, std::min({n_cu, 256, (nbr + 1) / 2}));
@@ -1449,7 +1435,7 @@ int build_bsr(bsgpu_ctx* c) {
       // ---- the coarse space of the two-level preconditioner: the free poses.  A pose = a 3-vector block next to a quaternion block in
       // a factor's variable list ((p, q) in the pose-graph types, (q, p) in the IMU ones); a pose that a one-pose factor holds (absolute
       // pose, IMU prior) is anchored and stays out.  BSGPU_PCG_COARSE=0: block-Jacobi alone (the cross-check).
-      const char* ce = getenv("BSGPU_PCG_COARSE");
+      const char* ce = env_str("BSGPU_PCG_COARSE");
       if (P.G > 0 && !(ce && !strcmp(ce, "0"))) {
         std::vector<int> p_of_q(c->nb, -1);
         std::vector<unsigned char> anchored(c->nb, 0);

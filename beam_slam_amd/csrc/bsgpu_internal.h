@@ -147,7 +147,7 @@ struct Visual {
   // NO C ROWS (round 6).  landmark_kernel's second pass wrote C = B Linv^T and rho = r - C z per observation (64 B) for the pair phase and the
   // back-substitution to read: 6.5 of its 22 us on C2 (measured with the pass taken out).  When EVERY landmark is a band landmark (no pair
   // entries, no factors of constant landmarks) the two consumers form C and rho themselves from the B rows (48 B, which they have or read instead)
-  // and the landmark's Linv and z: lone solves pass CR = nullptr to the three launches; the batched launches keep the C rows.  BSGPU_NO_CR=0: never.
+  // and the landmark's Linv and z: the three launches get CR = nullptr, lone and batched alike, and v.CR is never written for such a window.  BSGPU_NO_CR=0: never.
   bool no_cr = false;
   // COMPACT POSE PART.  Pose-part pitch of J in doubles: kJAStride, or kJACompact when the window keeps no translation columns (48 B per factor less written
   // by the evaluation and read by the band kernel and the back-substitution).  Chosen at finalize for the windows without C rows (no_cr: no factor

@@ -6,6 +6,7 @@
 #include <thread>
 
 #include "bsgpu_ctx.h"
+#include "bsgpu_env.h"
 #include "lm_state.h"
 
 namespace bsg {
@@ -118,7 +119,7 @@ bool pcg_check(bsgpu_ctx* c) {
   double done = c->h_pcg_lazy[pcg_done_slot()];
   const double iters = c->h_pcg_lazy[pcg_iters_slot()];
   // (tests: BSGPU_PCG_GIVE_UP=n declares the n-th verdict of the process a failure — the path a shared device takes)
-  if (const char* e = getenv("BSGPU_PCG_GIVE_UP")) { if (++c->pcg_verdicts_seen == atoi(e)) done = 0.0; }   // (counted per context)
+  if (const char* e = env_str("BSGPU_PCG_GIVE_UP")) { if (++c->pcg_verdicts_seen == atoi(e)) done = 0.0; }   // (counted per context)
   if (done > 0.0) { c->pcg_iters_total += (int)iters; return true; }
   fprintf(stderr, "[bsgpu] the resident PCG launch was given up (done %g after %g iterations): launch-per-iteration path from here on\n", done, iters);
   c->pcg_persist.G = 0;
@@ -186,7 +187,7 @@ void spcg_solve(bsgpu_ctx* c, const bsgpu_options& o) {
 // model-cost terms ride in the launches of the window's other pose-only factors instead of three launches of their own behind them
 // (BSGPU_MARG_RIDE=0: the launches of their own; several priors: the first one rides)
 static int marg_rider(const bsgpu_ctx* c) {
-  static const bool off = getenv("BSGPU_MARG_RIDE") && atoi(getenv("BSGPU_MARG_RIDE")) == 0;
+  static const bool off = env_zero("BSGPU_MARG_RIDE");
   if (off || c->use_graphs) return -1;
   for (size_t i = 0; i < c->marg.size(); ++i)
     if (c->marg[i].active && c->marg[i].dev.rows > 0) return (int)i;
@@ -204,7 +205,7 @@ void eval_all(bsgpu_ctx* c, const double* x, bool with_J, int slot, const Reduce
   const bool imu_pair = c->small[BSGPU_F_IMU_DELTA].n + c->small[BSGPU_F_IMU_PRIOR].n > 0;
   // (a visual-inertial window: the IMU factors ride in the reprojection launch — the cost-only pass always, the pass with Jacobians
   // unless BSGPU_EVAL_MERGE=0: there the IMU body's registers cost the reprojection kernel a wave of occupancy per SIMD)
-  static const int merge_mode = getenv("BSGPU_EVAL_MERGE") ? atoi(getenv("BSGPU_EVAL_MERGE")) : 2;   // 0: never, 1: cost-only passes, 2: both
+  static const int merge_mode = env_eval_merge();   // 0: never, 1: cost-only passes, 2: both
   const bool merged = imu_pair && c->vis.n > 0 && (with_J ? merge_mode >= 2 : merge_mode >= 1);
   // (a free extrinsic pair: its derived camera entries from the values this evaluation reads, so that the kernels below stay as they are)
   if (c->calib.on) launch_calib_refresh(s, c->calib, x, c->d_cams);
@@ -243,7 +244,7 @@ void eval_all(bsgpu_ctx* c, const double* x, bool with_J, int slot, const Reduce
       if (t == rel_t || t == BSGPU_F_UNICYCLE || !c->small[t].n) continue;
       gs[ng] = c->small[t]; ps[ng] = cand ? c->d_small_part_cand[t] : c->d_small_part[t]; ++ng;
     }
-    static const bool separate = getenv("BSGPU_EVAL_SEPARATE") != nullptr;
+    static const bool separate = env_set("BSGPU_EVAL_SEPARATE");
     const int mr = separate ? -1 : marg_rider(c);
     if (mr >= 0 && launch_small_eval_set_marg(s, gs, ps, ng, x, c->d_losses, with_J, c->marg[mr].dev, cand ? c->marg[mr].part_cand : c->marg[mr].part))
       marg_done = mr;
@@ -260,12 +261,12 @@ void eval_all(bsgpu_ctx* c, const double* x, bool with_J, int slot, const Reduce
 // window on eager launches whose host polls the mirror's stamp, outside bsgpu_profile_step (which times the reduction in its own phase)
 // (what any riding reduction needs: eager launches, a host that polls the mirror's stamp, outside bsgpu_profile_step)
 bool reduce_can_ride(const bsgpu_ctx* c) {
-  static const bool by_event = getenv("BSGPU_SCALARS_EVENT") != nullptr, off = getenv("BSGPU_REDUCE_LAUNCH") != nullptr;
+  static const bool by_event = env_scalars_event(), off = env_reduce_launch();
   return !off && !by_event && !c->use_graphs && !c->use_pcg && !c->prof_events && c->h_scal_dev != nullptr && c->d_reduce_counter != nullptr && c->n_reduce > 0;
 }
 bool reduce_rides(const bsgpu_ctx* c) {
-  static const bool by_event = getenv("BSGPU_SCALARS_EVENT") != nullptr, off = getenv("BSGPU_REDUCE_LAUNCH") != nullptr;
-  static const int merge_mode = getenv("BSGPU_EVAL_MERGE") ? atoi(getenv("BSGPU_EVAL_MERGE")) : 2;
+  static const bool by_event = env_scalars_event(), off = env_reduce_launch();
+  static const int merge_mode = env_eval_merge();
   const bool imu_pair = c->small[BSGPU_F_IMU_DELTA].n + c->small[BSGPU_F_IMU_PRIOR].n > 0;
   // (the launch that carries it: the visual-inertial evaluation, or a lidar-inertial window's relative-pose + IMU evaluation — eval_all)
   const bool carrier = imu_pair && merge_mode >= 2 && (c->vis.n > 0 || c->small[BSGPU_F_RELPOSE_EXT].n > 0 || c->small[BSGPU_F_RELPOSE].n > 0);
@@ -274,7 +275,7 @@ bool reduce_rides(const bsgpu_ctx* c) {
 }
 void final_reduce(bsgpu_ctx* c) {
   // (BSGPU_SCALARS_EVENT=1: the host waits for an event recorded behind the reduction instead of polling the mirror's stamp)
-  static const bool by_event = getenv("BSGPU_SCALARS_EVENT") != nullptr;
+  static const bool by_event = env_scalars_event();
   const bool stamp = !c->use_graphs && !by_event && c->h_scal_dev != nullptr && c->d_reduce_counter != nullptr && c->n_reduce > 0;
   if (stamp) c->reduce_seq += 1.0;
   launch_final_reduce(c->stream, c->d_reduce, c->n_reduce, SC_GRAD_NORM2 + 1, c->d_scal, c->h_scal_dev, stamp ? c->d_reduce_counter : nullptr, c->reduce_seq);
@@ -335,9 +336,8 @@ void assemble(bsgpu_ctx* c, const bsgpu_options& o, double radius, bool new_J, b
     if (c->vis.n_seg > 0 || band) units = small_assemble_first_set(c->small_factorwise + 2, kNumInternal - 2, &set, &taken);
     if (units == 0) taken = 0;
     // (the band units add to the lower triangle only where the fused tiled factorisation is what reads the system next: enqueue_step's assemblies — the
-    //  covariance / marginalisation entry points, the PCG on the reduced system and the launch-per-step fallback get both triangles.  BSGPU_BAND_LOWER=0: always both)
-    static const bool lower_off = getenv("BSGPU_BAND_LOWER") && atoi(getenv("BSGPU_BAND_LOWER")) == 0;
-    const bool lower_only = !lower_off && factor_follows && !gradient_only && !c->use_spcg && !c->use_pcg && c->dense_ok && c->d_ftasks && c->d_fsync && c->d_tile_tot && c->d_Winv;
+    //  covariance / marginalisation entry points, the PCG on the reduced system and the launch-per-step fallback get both triangles)
+    const bool lower_only = factor_follows && !gradient_only && !c->use_spcg && !c->use_pcg && c->dense_ok && c->d_ftasks && c->d_fsync && c->d_tile_tot && c->d_Winv;
     if (band) launch_pairs_band(s, c->vis, c->d_S, c->npad, c->plan.rhs_row, c->d_grad, c->d_hdiag, c->d_dpos, gradient_only, units > 0 ? &set : nullptr, units, lower_only, go);
     launch_pairs(s, c->vis, c->d_S, c->npad, c->plan.rhs_row, c->d_grad, c->d_hdiag, c->d_dpos, gradient_only, (units > 0 && !band) ? &set : nullptr, band ? 0 : units, go);
     // (a free extrinsic pair: the border S(i,e), S(e,e), rhs(e), g_e, diag(H)_e — behind the landmark launch, whose C rows it reads)
@@ -495,7 +495,7 @@ void linear_solve_and_candidate(bsgpu_ctx* c, const bsgpu_options& o, bool defer
     }
     // ... and the next step's clearing with it (the factorisation of this step is done; nothing reads S, the gradient or the diagonal
     // before the next assembly) — when the end-of-step reduction mirrors the scalars (it then clears the factorisation's flag)
-    static const bool clear_at_start = getenv("BSGPU_CLEAR_AT_START") != nullptr;
+    static const bool clear_at_start = env_clear_at_start();
     ZeroStep zn;
     const bool ride_zero = c->upd_in_mcc && !c->use_pcg && !c->use_graphs && c->dense_ok && c->h_scal_dev != nullptr && !clear_at_start;
     if (ride_zero) {
@@ -551,7 +551,7 @@ void enqueue_step(bsgpu_ctx* c, const bsgpu_options& o, int kind, double radius,
   const bool assembled_ahead = kind == STEP_ACCEPT && !gradient_only && radius > 0.0 && (c->spec_lm_radius == radius || dev_confirmed);
   const bool ahead_unconfirmed = c->spec_dirty && !assembled_ahead;
   if (assembled_ahead && dev_confirmed) c->lm_diag.inv_radius = 1.0 / radius;   // (the assembly configured the LM diagonal's tasks with a placeholder)
-  static const bool log_refusals = getenv("BSGPU_TIMING") != nullptr;
+  static const bool log_refusals = env_timing();
   if (log_refusals && c->spec_dev && !assembled_ahead)
     fprintf(stderr, "[bsgpu] device decision not adopted: host kind %d radius %.17g, device go %g radius %.17g\n", kind, radius, c->h_scal[SC_DEC_GO], c->h_scal[SC_DEC_RADIUS]);
   c->spec_lm_radius = 0.0; c->spec_dirty = false; c->spec_dev = false;
@@ -575,7 +575,6 @@ void enqueue_step(bsgpu_ctx* c, const bsgpu_options& o, int kind, double radius,
   // With an assembly ahead (radius_ahead) the candidate is evaluated ONCE: with Jacobians, into the candidate's cost partials — the
   // cost-only pass in front of it computed the same residuals — and the step's reduction rides in the assembly's first launch, which follows
   // that evaluation (4.7 us + a launch boundary less per iteration of a reference-sized window, 5.2 of C3's).
-  static const bool one_pass_off = getenv("BSGPU_CAND_ONE_PASS") && atoi(getenv("BSGPU_CAND_ONE_PASS")) == 0;
   // (an assembly ahead is adopted only when the LM diagonal and the gradient norms ride in the factorisation — diag_in_chol's static
   //  preconditions — and it zeroes scalar slots the host must already have read through the mirror: without either it would be assembled
   //  and thrown away every iteration, or the host would read a zeroed gradient norm)
@@ -583,7 +582,7 @@ void enqueue_step(bsgpu_ctx* c, const bsgpu_options& o, int kind, double radius,
   const bool mirror_ok = c->h_scal_dev != nullptr && c->d_reduce_counter != nullptr && c->n_reduce > 0;
   bool ahead = radius_ahead > 0.0 && !c->use_graphs && !c->use_pcg && !c->use_spcg && c->dense_ok && c->n_pose > 0 && c->idp.n_lm == 0 &&
                diag_can_ride && mirror_ok;
-  bool one_pass = ahead && !one_pass_off && reduce_can_ride(c) && (c->vis.n_lm > 0 || (c->n_sa_seg + c->n_asm_grp > 0 && marg_rider(c) < 0));
+  bool one_pass = ahead && reduce_can_ride(c) && (c->vis.n_lm > 0 || (c->n_sa_seg + c->n_asm_grp > 0 && marg_rider(c) < 0));
   // (the decision on the device rides in the landmark launch of a one-pass assembly: without one there is no assembly ahead at all — radius_ahead is no guess)
   const bool dev = lmd != nullptr && lmd->on;
   if (dev && !(one_pass && c->vis.n_lm > 0 && c->d_dec != nullptr)) ahead = one_pass = false;
@@ -606,7 +605,7 @@ void enqueue_step(bsgpu_ctx* c, const bsgpu_options& o, int kind, double radius,
       // With the decision on the device the reduction is split: only the candidate's cost waits for the evaluation — every other unit rides in the
       // evaluation's launch (as under `ride`), and the landmark launch carries that one unit, which finds the others' scalars done and decides two
       // memory round trips into the launch (all eight units there: the decision came 18 us into a 15 us launch, behind the landmark waves' loads).
-      static const bool split_off = getenv("BSGPU_LM_DEVICE_SPLIT") && atoi(getenv("BSGPU_LM_DEVICE_SPLIT")) == 0;
+      static const bool split_off = env_zero("BSGPU_LM_DEVICE_SPLIT");
       const bool split = dev && !split_off && reduce_rides(c);
       if (split) {
         ReduceRide re = r;
@@ -614,9 +613,8 @@ void enqueue_step(bsgpu_ctx* c, const bsgpu_options& o, int kind, double radius,
         eval_all(c, c->d_xcand, true, SC_COST_CAND, &re);
         r.only_slot = SC_COST_CAND;
         // (its arrays in the launch's arguments when they fit the unit's one-trip form: at most four, sums, one of up to 4 096 values, the others of up to 256)
-        static const bool args_off = getenv("BSGPU_LM_DEVICE_ARGS") && atoi(getenv("BSGPU_LM_DEVICE_ARGS")) == 0;
         int ne = 0, n_big = 0;
-        bool fits = !args_off;
+        bool fits = true;
         for (const ReduceEntry& en : c->h_reduce) {
           if (en.slot != SC_COST_CAND) continue;
           if (ne == 4 || en.op != 0 || en.n > 4096) { fits = false; break; }
@@ -640,7 +638,7 @@ void enqueue_step(bsgpu_ctx* c, const bsgpu_options& o, int kind, double radius,
       else { c->reduce_seq -= 1.0; final_reduce(c); }   // (no launch of this window's assembly takes it: a launch of its own)
       c->spec_dirty = true;
       c->spec_lm_radius = (c->diag_in_chol && !dev) ? radius_ahead : 0.0;
-      c->spec_dev = c->diag_in_chol && dev && lmd->on == 1 && c->reduce_carried;   // (on == 2, the timing probe whose landmark waves took a placeholder radius: never adopted)
+      c->spec_dev = c->diag_in_chol && dev && c->reduce_carried;
       c->prof_events = prof;
       return;
     }
@@ -743,7 +741,7 @@ void build_graphs(bsgpu_ctx* c, const bsgpu_options& o) {
     if (e != hipSuccess) { (void)hipGetLastError(); c->destroy_graphs(); c->graphs_tried = true; return; }
   }
   c->graphs_ok = true;
-  if (getenv("BSGPU_TIMING")) fprintf(stderr, "[bsgpu] LM step captured as hipGraphs\n");
+  if (env_timing()) fprintf(stderr, "[bsgpu] LM step captured as hipGraphs\n");
 }
 
 void run_step(bsgpu_ctx* c, const bsgpu_options& o, int kind, double radius, bool gradient_only = false, double radius_ahead = 0.0, const LmDecide* lmd = nullptr) {
@@ -1042,7 +1040,7 @@ int solve(bsgpu_ctx* c, const bsgpu_options& o, bsgpu_summary& sum) {
   lm.t_start = t_start;
   // the assembly of the step after this one goes out ahead of the decision (enqueue_step) where it is short — a wrong guess costs its
   // length: nothing on the reference's window sizes, C2's three guesses in ten that miss cost more than the seven that hit gain (measured)
-  static const int ahead_env = getenv("BSGPU_LM_AHEAD") ? atoi(getenv("BSGPU_LM_AHEAD")) : -1;
+  static const int ahead_env = env_int("BSGPU_LM_AHEAD", -1);
   // (a free extrinsic pair: host-decided steps — no assembly ahead, no decision on the device)
   const bool lm_ahead = !c->calib.on && (ahead_env >= 0 ? ahead_env != 0 : (c->vis.n <= kAssemblyAheadMaxFactors && c->n_res <= kAssemblyAheadMaxResiduals));   // (pose-only windows too: their assembly takes no radius, only the guess "accepted")
   // (the radius of LmState::advance for a relative decrease above 0.937, in its own arithmetic: r / (1/3) is not 3 r in every last bit)
@@ -1050,13 +1048,13 @@ int solve(bsgpu_ctx* c, const bsgpu_options& o, bsgpu_summary& sum) {
   // fifth to seventh) the next assembly waits for the decision again, until a step ends that way
   // Windows above those sizes: the assembly ahead at the radius the DEVICE decides (enqueue_step, LmDecide) — no guess that can miss, and the
   // candidate's cost-only pass goes.  BSGPU_LM_DEVICE=0: never, 1: on the smaller windows too (instead of their guesses).
-  static const int dev_env = getenv("BSGPU_LM_DEVICE") ? atoi(getenv("BSGPU_LM_DEVICE")) : -1;
+  static const int dev_env = env_int("BSGPU_LM_DEVICE", -1);
   const bool dev_possible = !c->calib.on && dev_env != 0 && ahead_env != 0 && c->vis.n_lm > 0 && c->d_dec != nullptr && !c->use_graphs && !c->use_pcg && !c->use_spcg;
   // (a smaller window whose last guess missed waits for the host's decision until a step ends as guessed again; the device deciding for it
   //  meanwhile measured the same — scripts/rejected_steps.py, 50 KF x 5 000 with four rejected steps in twenty: 6 700 LM it/s either way)
   const bool lm_dev = dev_possible && (dev_env > 0 || !lm_ahead);
   LmDecide lmd;
-  lmd.on = dev_possible ? (getenv("BSGPU_LM_DEVICE_NOWAIT") ? 2 : 1) : 0;   // (2: a timing probe — the landmark waves do not wait, the assembly is never adopted)
+  lmd.on = dev_possible ? 1 : 0;
   lmd.min_relative_decrease = o.min_relative_decrease; lmd.max_radius = o.max_trust_region_radius; lmd.function_tolerance = o.function_tolerance;
   lmd.parameter_tolerance = o.parameter_tolerance; lmd.gradient_tolerance = o.gradient_tolerance;
   bool guess_held = true;
@@ -1081,7 +1079,7 @@ int solve(bsgpu_ctx* c, const bsgpu_options& o, bsgpu_summary& sum) {
       // workgroups were not scheduled in time — not a numerical failure.  This context takes the launch-per-step path from
       // here on, and the step is computed again at the same point and radius.
       c->d_ftasks = nullptr;
-      if (getenv("BSGPU_TIMING")) fprintf(stderr, "[bsgpu] single-launch Cholesky timed out: launch-per-step path from here on\n");
+      if (env_timing()) fprintf(stderr, "[bsgpu] single-launch Cholesky timed out: launch-per-step path from here on\n");
       if (c->use_graphs) { c->destroy_graphs(); build_graphs(c, o); }   // (the captured sequences still hold the single-launch kernel)
     }
     guess_held = lm.kind == STEP_ACCEPT && lm.radius == guessed;

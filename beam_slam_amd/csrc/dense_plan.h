@@ -108,7 +108,7 @@ struct DensePlan {
   std::vector<FusedTask> ftasks;
   std::vector<int> tile_tot;          // (T+1)^2: number of update TASKS per tile (what a chain waits for before it reads its tiles): updates that take a turn of their
                                       // own on the tile | kFusedSplit chunks << 16
-  int split_depth = 2;                // how many of the LAST updates of a tile inside a chain are dealt out as kFusedSplit chunks; 0: none (finalize: BSGPU_CHOL_SPLIT)
+  int split_depth = 2;                // how many of the LAST updates of a tile inside a chain are dealt out as kFusedSplit chunks; 0: none
   int n_split_chunks = 0;
   std::vector<int> fchain_begin, fchain_len, fchain_of_tile;   // the chains of the fused factorisation
   std::vector<int> fext_of;           // T+1: the appendix tile panel k carries (kFusedExt), or -1

@@ -19,6 +19,7 @@
 #include <thread>
 
 #include "bsgpu_device.h"
+#include "bsgpu_env.h"
 #include "chol_chain.h"
 #include "dense_plan.h"
 
@@ -1434,7 +1435,7 @@ int fused_sync_stride() {
 
 // how the updates of a launch reach their tiles (FusedCtx::no_turn): 0 turns (BSGPU_CHOL_NOTURN=0), 1 atomics behind a diagonal tile's LM-diagonal task, 2 atomics
 static int fused_update_mode(bool diag_tasks_in_list) {
-  static const bool turns = getenv("BSGPU_CHOL_NOTURN") && atoi(getenv("BSGPU_CHOL_NOTURN")) == 0;
+  static const bool turns = env_chol_turns();
   return turns ? 0 : diag_tasks_in_list ? 1 : 2;
 }
 void launch_chol_fused(hipStream_t s, double* S, double* Lp, int ld, const FusedTask* tasks_dev, int n_tasks, const int* tile_tot_dev, const int* nreal_dev,
@@ -1444,7 +1445,7 @@ void launch_chol_fused(hipStream_t s, double* S, double* Lp, int ld, const Fused
   const int grid = n_tasks;   // one workgroup per task (about 100 KB of LDS each: one per CU is resident, the rest queue behind them)
   // BSGPU_CHOL_PROBE=<file>: the 20th factorisation of the process runs the stamped variant and dumps, per task, the wall-clock
   // stamps (100 MHz) dequeue / got task / dependencies met / tiles in LDS / solves done / update done / published, and its workgroup
-  static const char* probe_file = getenv("BSGPU_CHOL_PROBE");
+  static const char* probe_file = env_str("BSGPU_CHOL_PROBE");
   static int probe_calls = 0;
   if (probe_file && ++probe_calls == 20) {
     long long* ts = nullptr;
@@ -2004,15 +2005,15 @@ bool launch_chol_backsolve_fused(hipStream_t s, const double* Lp, const double* 
     if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) n_cu = pr.multiProcessorCount;
     if (n_cu <= 0) n_cu = 256;
   }
-  static const bool off = getenv("BSGPU_BACKSOLVE_FUSED") && atoi(getenv("BSGPU_BACKSOLVE_FUSED")) == 0;
+  static const bool off = env_zero("BSGPU_BACKSOLVE_FUSED");
   const size_t lds = chol_backsolve_chain_lds(npad, max_chain_len) + 16;
   (void)n_cu;   // (roles are ticketed in dependency order: the grid need not be resident at once; beyond ~2 workgroups per CU the
                 // launch-per-level form is the better one)
-  if (off || !Winv || !order_dev || n_chains + n_items > 2 * n_cu || lds > (size_t)160 * 1024 - 256 /* (4 bytes of static LDS) */ || getenv("BSGPU_BACKSOLVE_GLOBAL_Y")) return false;
+  if (off || !Winv || !order_dev || n_chains + n_items > 2 * n_cu || lds > (size_t)160 * 1024 - 256 /* (4 bytes of static LDS) */ || env_backsolve_global_y() >= 0) return false;
   const bool deep = max_rows > 0 && max_rows <= kBsChunkDeep && max_chain_len > 1;
   // BSGPU_BACKSOLVE_PROBE=<file>: the 20th solve of the process is stamped (100 MHz wall clock): per workgroup start / loads out /
   // turn / start values / after each panel / done
-  static const char* probe_file = getenv("BSGPU_BACKSOLVE_PROBE");
+  static const char* probe_file = env_str("BSGPU_BACKSOLVE_PROBE");
   static int probe_calls = 0;
   long long* ts = nullptr;
   const int grid = n_chains + n_items;
@@ -2054,10 +2055,10 @@ void launch_chol_backsolve_chains(hipStream_t s, const double* S, const double* 
   size_t lds = chol_backsolve_chain_lds(npad, max_chain_len);
   // Winv (the tiles' full inverses, left by the fused factorisation): a panel's own solve is two 16-part reductions instead of a
   // substitution with 64 dependent pivots (bs_chain_walk)
-  static const bool no_w = getenv("BSGPU_BACKSOLVE_NO_W") != nullptr;
+  static const bool no_w = env_backsolve_no_w();
   if (no_w) Winv = nullptr;
-  const char* fg = getenv("BSGPU_BACKSOLVE_GLOBAL_Y");   // (tests: force the path windows above 12 288 reduced dimensions take)
-  const int y_in_lds = (lds <= (size_t)160 * 1024 && !(fg && atoi(fg) != 0)) ? 1 : 0;
+  // (BSGPU_BACKSOLVE_GLOBAL_Y=1, tests: force the path windows above 12 288 reduced dimensions take)
+  const int y_in_lds = (lds <= (size_t)160 * 1024 && env_backsolve_global_y() <= 0) ? 1 : 0;
   if (!y_in_lds) lds = chol_backsolve_chain_lds(0, max_chain_len);
   // max_rows: the most row tiles any panel of these chains has (0: unknown).  Few enough: the two-panel-deep variant.
   const bool deep = max_rows > 0 && max_rows <= kBsChunkDeep && max_chain_len > 1;
@@ -2141,7 +2142,7 @@ int batchargs_backsolve(BatchArgTable* tabs, const DensePlan& P, const DenseDev&
   chol_backsolve_chain_kernel_Args c;
   f.bsg_grid = 0; c.bsg_grid = 0;
   size_t lds = 0;
-  if (level_sync && D.bs_items4 && D.bs_sync && D.scal && D.Winv && D.ftasks && D.fsync && D.bs_order && !getenv("BSGPU_BACKSOLVE_GLOBAL_Y")) {
+  if (level_sync && D.bs_items4 && D.bs_sync && D.scal && D.Winv && D.ftasks && D.fsync && D.bs_order && env_backsolve_global_y() < 0) {
     for (int g = 0; g < G; ++g) max_rows = std::max(max_rows, P.bs_group_maxrows[g]);
     max_rows = std::max(1, max_rows);
     const int n_chains = (int)P.chain_begin.size(), n_items = (int)P.bs_upd.size() / 3 * (P.bs_upd_off.back() > 0 ? 1 : 0);
@@ -2155,8 +2156,8 @@ int batchargs_backsolve(BatchArgTable* tabs, const DensePlan& P, const DenseDev&
       f.upd_rows = D.bs_upd_rows; f.tile_updated = D.bs_tile_updated; f.y = y; f.npad = P.npad; f.max_len = max_len; f.y_init = rhs_row; f.iperm = iperm; f.n_pose = n_pose;
       f.y_tan = y_tan; f.delta = delta; f.sync = D.bs_sync; f.scal = D.scal; f.ts = nullptr; f.order = D.bs_order; f.fs = fused_sync_stride();
     }
-  } else if (!level_sync && G == 1 && P.chain_begin.size() == 1 && D.ftasks && D.fsync && D.tile_tot && D.Winv && !getenv("BSGPU_BACKSOLVE_GLOBAL_Y") &&
-             !getenv("BSGPU_BACKSOLVE_NO_W")) {
+  } else if (!level_sync && G == 1 && P.chain_begin.size() == 1 && D.ftasks && D.fsync && D.tile_tot && D.Winv && env_backsolve_global_y() < 0 &&
+             !env_backsolve_no_w()) {
     lds = chol_backsolve_chain_lds(P.npad, max_len);
     if (lds <= (size_t)160 * 1024) {
       const bool deep = false;   // (max_rows unknown for the plain row lists: launch_chol_backsolve_chains passes 0)

@@ -16,6 +16,7 @@
 #include <atomic>
 
 #include "bsgpu_device.h"
+#include "bsgpu_env.h"
 
 namespace bsg {
 
@@ -1064,7 +1065,7 @@ bool launch_pcg_persistent(hipStream_t s, const PcgPersistDev& P, int nbr, const
   if (hipMemsetAsync(P.slots, 0xff, P.sync_bytes, s) != hipSuccess) { (void)hipGetLastError(); return false; }
   const long long timeout_ticks = 100000000LL / 5;   // s_memrealtime: 100 MHz; a fifth of a second for the whole solve
   // BSGPU_PCG_PROBE=1: workgroup 0 stamps the phases of its first 64 iterations with the 100 MHz wall clock; printed once
-  static const bool want_probe = getenv("BSGPU_PCG_PROBE") != nullptr;
+  static const bool want_probe = env_set("BSGPU_PCG_PROBE");
   static long long* d_probe = nullptr;
   static int probe_left = 3;
   long long* probe = nullptr;

@@ -209,7 +209,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     return;
   }
   landmark_kernel_body((int)blockIdx.x - n_units, (int)gridDim.x - n_units, n_lm, lm_start, JB, r, n_pose, radius_ptr, compute_scale, compute_dcl, jacobi, lm_lo, lm_hi, scale, dcl, grad, Linv_out, z_out, CR, lm_blocks, zs, radius_val,
-                       (red.lmd.on && red.lmd.on != 2) ? red.dec : nullptr);
+                       (red.lmd.on && red.lmd.on != 2) ? red.dec : nullptr);   // (lmd.on is 0 or 1; the second test is left from a removed probe mode so that this kernel's code stays what it was)
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
 struct landmark_kernel_Args {

@@ -1,4 +1,4 @@
-# A/B of the dissection's separator absorption and hand-over constant on one box: bash scripts/ab_absorb.sh
+# A/B of the dissection's separator absorption on one box: bash scripts/ab_absorb.sh
 run() { python bench.py --full --workload $1 --steps 15 --warmup 3 --no-cpu-baseline --no-past-l3 --no-other-configs --sustained-seconds 0 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
@@ -7,7 +7,7 @@ for l in sys.stdin:
 "; }
 for rep in 1 2; do
 for w in c2 c3; do
-  for hop in ${HOPS:-10 7 6 5 4}; do BSGPU_DIM_ABSORB=1 BSGPU_DIM_T_HOP=$hop run $w absorb=1,hop=$hop; done
+  for a in 0 1; do BSGPU_DIM_ABSORB=$a run $w absorb=$a; done
 done
 done
-for hop in ${HOPS:-10 7 6 5 4}; do echo hop=$hop; BSGPU_DIM_ABSORB=1 BSGPU_DIM_T_HOP=$hop python scripts/small_window.py | tail -4; done
+for a in 0 1; do echo absorb=$a; BSGPU_DIM_ABSORB=$a python scripts/small_window.py | tail -4; done

@@ -1,5 +1,5 @@
 """Aggregate LM iterations/s of N independent windows on ONE GPU through bsgpu_solve_batch — the batched launches (one set per LM
-iteration for all windows, csrc/bsgpu_batch.cpp) against the thread-per-window form (BSGPU_BATCH_THREADS=1) and the lone solve.
+iteration for all windows, csrc/bsgpu_batch.cpp) against the lone solve.
     python scripts/batch_windows.py --size 20:500 1 8 32 64
 The windows are the reference's own sizes (vio.yaml:3,56: tens of key frames) or C2-shaped (BASELINE config 5 on one device)."""
 import os, sys, time
@@ -17,11 +17,10 @@ windows = [synthetic.vio_window(n_kf=n_kf, n_lm=n_lm, seed=20250630 + i) for i i
 solvers = []
 for pr in windows:
     g = GpuSolver(0); pr.load(g)
-    if max(counts) > 1 and not os.environ.get("BSGPU_BATCH_LATENCY_PLANS"): g.set_plan_preference(True)   # (BSGPU_PLAN_THROUGHPUT: one of many)
+    if max(counts) > 1: g.set_plan_preference(True)   # (planned for throughput: one of many)
     g.finalize(); solvers.append(g)
 opt = solvers[0].options_vio(); opt.max_solver_time_in_seconds = 0.0
-mode = "thread per window" if os.environ.get("BSGPU_BATCH_THREADS") else "batched launches"
-print("windows of %d key frames x %d landmarks, bsgpu_solve_batch: %s" % (n_kf, n_lm, mode), flush=True)
+print("windows of %d key frames x %d landmarks, bsgpu_solve_batch" % (n_kf, n_lm), flush=True)
 for n in counts:
     sv = solvers[:n]
     for _ in range(3):

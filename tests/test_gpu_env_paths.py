@@ -56,6 +56,13 @@ def _run(env_extra, window="vio"):
     return json.loads(out.stdout.strip().splitlines()[-1])
 
 
+def _same_optimum(r, d):
+    """the run under a switch against the default run of the same window: the same accepted / rejected steps, cost and values"""
+    assert r["it"] == d["it"] and r["acc"] == d["acc"]
+    assert abs(r["cost"] - d["cost"]) <= 1e-9 * d["cost"]
+    assert max(abs(a - b) for a, b in zip(r["x"], d["x"])) < 1e-7
+
+
 @pytest.fixture(scope="module")
 def default_run():
     return _run({})
@@ -76,6 +83,7 @@ SETTINGS = [
     {"BSGPU_POSE_DIAG_LAUNCH": "1", "BSGPU_CHOL_EXT": "0"},
     {"BSGPU_CHOL_EXT": "0"},                                     # a separator's appendix tile (<= 16 real columns) as a panel of its own instead of riding in the tasks of the panel before it
     {"BSGPU_CHOL_EXT": "0", "BSGPU_CHOL_FUSED": "0"},
+    {"BSGPU_CHOL_NOTURN": "0"},                                  # the factorisation's updates in turn order (a bit-reproducible factor) instead of FP64 atomics in no particular order
     {"BSGPU_DIM_ORDER": "0"},                                    # the tile-level nested dissection (runs of natural tiles) instead of the per-dimension order
     {"BSGPU_DIM_ORDER": "0", "BSGPU_CHAINS": "4"},
     {"BSGPU_DIM_ORDER_DEPTH": "2"},                              # a shallower dissection: fewer, larger pieces
@@ -95,11 +103,7 @@ SETTINGS = [
 
 @pytest.mark.parametrize("setting", SETTINGS, ids=lambda s: ",".join("%s=%s" % kv for kv in s.items()))
 def test_alternative_path_reaches_the_same_optimum(default_run, setting):
-    r = _run(setting)
-    d = default_run
-    assert r["it"] == d["it"] and r["acc"] == d["acc"]
-    assert abs(r["cost"] - d["cost"]) <= 1e-9 * d["cost"]
-    assert max(abs(a - b) for a, b in zip(r["x"], d["x"])) < 1e-7
+    _same_optimum(_run(setting), default_run)
 
 
 # the inverse-depth window (landmark-side elimination, k_idp.hip) under the switches that change what runs around it
@@ -122,11 +126,7 @@ def default_idp_run():
 
 @pytest.mark.parametrize("setting", IDP_SETTINGS, ids=lambda s: ",".join("%s=%s" % kv for kv in s.items()))
 def test_inverse_depth_window_under_alternative_paths(default_idp_run, setting):
-    r = _run(setting, "idp")
-    d = default_idp_run
-    assert r["it"] == d["it"] and r["acc"] == d["acc"]
-    assert abs(r["cost"] - d["cost"]) <= 1e-9 * d["cost"]
-    assert max(abs(a - b) for a, b in zip(r["x"], d["x"])) < 1e-7
+    _same_optimum(_run(setting, "idp"), default_idp_run)
 
 
 # a lidar-inertial window (relative-pose constraints with extrinsics + IMU factors, no landmarks)
@@ -147,11 +147,7 @@ def default_lio_run():
 
 @pytest.mark.parametrize("setting", LIO_SETTINGS, ids=lambda s: ",".join("%s=%s" % kv for kv in s.items()))
 def test_lidar_inertial_window_under_alternative_paths(default_lio_run, setting):
-    r = _run(setting, "lio")
-    d = default_lio_run
-    assert r["it"] == d["it"] and r["acc"] == d["acc"]
-    assert abs(r["cost"] - d["cost"]) <= 1e-9 * d["cost"]
-    assert max(abs(a - b) for a, b in zip(r["x"], d["x"])) < 1e-7
+    _same_optimum(_run(setting, "lio"), default_lio_run)
 
 
 # a window that carries a dense marginal prior (fixed_lag_smoother.cpp:269-272)
@@ -170,11 +166,7 @@ def default_prior_run():
 
 @pytest.mark.parametrize("setting", PRIOR_SETTINGS, ids=lambda s: ",".join("%s=%s" % kv for kv in s.items()))
 def test_window_with_dense_prior_under_alternative_paths(default_prior_run, setting):
-    r = _run(setting, "prior")
-    d = default_prior_run
-    assert r["it"] == d["it"] and r["acc"] == d["acc"]
-    assert abs(r["cost"] - d["cost"]) <= 1e-9 * d["cost"]
-    assert max(abs(a - b) for a, b in zip(r["x"], d["x"])) < 1e-7
+    _same_optimum(_run(setting, "prior"), default_prior_run)
 
 
 @pytest.fixture(scope="module")
@@ -185,8 +177,4 @@ def default_lio_prior_run():
 @pytest.mark.parametrize("setting", [{"BSGPU_MARG_RIDE": "0"}, {"BSGPU_EVAL_SEPARATE": "1"}], ids=lambda s: ",".join("%s=%s" % kv for kv in s.items()))
 def test_lidar_inertial_window_with_dense_prior_under_alternative_paths(default_lio_prior_run, setting):
     """no landmark launches to ride in: the prior's evaluation and assembly ride with the relative-pose factors', its model-cost terms go by themselves"""
-    r = _run(setting, "lio_prior")
-    d = default_lio_prior_run
-    assert r["it"] == d["it"] and r["acc"] == d["acc"]
-    assert abs(r["cost"] - d["cost"]) <= 1e-9 * d["cost"]
-    assert max(abs(a - b) for a, b in zip(r["x"], d["x"])) < 1e-7
+    _same_optimum(_run(setting, "lio_prior"), default_lio_prior_run)

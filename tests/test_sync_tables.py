@@ -222,6 +222,55 @@ def test_resident_table_flattens_to_the_same_tables(gpu_solver_cls, monkeypatch)
 
 
 @pytest.mark.gpu
+def test_forced_full_hand_over_equals_the_change_lists(gpu_solver_cls, monkeypatch):
+    """BSGPU_SYNC_FULL=1 (read at every call: set here around one context's syncs only) reads the whole table whatever the change
+    list says — the path a first call, a rejected call or a grown table takes.  The same sequence of syncs leaves the same tables
+    (residuals, Jacobian, screening errors bit for bit) and the same solve as the context patched by the change lists.
+    (The two solves run on identical tables and differ by the order of FP64 atomics only: compared as _cycles compares two such solves.)"""
+    monkeypatch.setenv("BSGPU_FLATTEN", "device")
+    monkeypatch.setenv("BSGPU_SYNC_CHECK", "1")
+    w = SlidingWindow(np.random.default_rng(17), 7, 30, 40)
+    a, f = gpu_solver_cls(0), gpu_solver_cls(0)
+
+    def sync(g, blocks, changed, full):
+        vals, off, size, man, const, s2b = blocks
+        g.clear(); g.set_blocks(vals, off, size, man, const); g.set_cameras(w.camera())
+        if full:
+            monkeypatch.setenv("BSGPU_SYNC_FULL", "1")
+        try:
+            g.sync_factors_indirect(capi.F_REPROJ, w.idx, s2b, w.consts, w.loss_kind, w.loss_a, changed)
+        finally:
+            monkeypatch.delenv("BSGPU_SYNC_FULL", raising=False)
+
+    for cyc in range(5):
+        if cyc:
+            w.drop_oldest(free_landmarks=cyc % 2 == 0)
+            w.add_keyframe()
+        blocks = w.blocks()
+        changed = w.take_dirty()
+        if cyc == 0:
+            changed = None   # (the first hand-over is whole for both)
+        sync(a, blocks, changed, False)
+        sync(f, blocks, changed, True)
+        ca, ra, ga, Ja = a.evaluate(jacobian=True)
+        cf, rf, gf, Jf = f.evaluate(jacobian=True)
+        assert ca == cf and np.array_equal(ra, rf) and np.array_equal(Ja, Jf), cyc
+        n = w.idx.shape[0]
+        assert np.array_equal(a.reprojection_errors(n), f.reprojection_errors(n)), cyc
+        sa, sf = a.solve(), f.solve()
+        assert sa.termination_type == sf.termination_type, cyc
+        assert abs(sa.final_cost - sf.final_cost) <= 1e-8 * sa.final_cost, cyc
+    # ... and it IS the whole table that is read: a row written behind the back of the change list, which BSGPU_SYNC_CHECK refuses
+    # in a patched hand-over (test_sync_rejects_bad_change_lists), arrives
+    w.consts[3, 1] += 2.0
+    blocks = w.blocks()
+    sync(f, blocks, np.array([], np.int32), True)
+    b = gpu_solver_cls(0)
+    _describe(w, b, blocks, False, False)
+    assert np.array_equal(f.evaluate()[1], b.evaluate()[1])
+
+
+@pytest.mark.gpu
 def test_rows_added_after_a_sync_join_the_table(gpu_solver_cls):
     """add_factors for the synced type in the same description: the mirrored rows and the appended ones are one group"""
     w = SlidingWindow(np.random.default_rng(23), 6, 25, 30)
