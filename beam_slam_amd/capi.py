@@ -114,7 +114,7 @@ SYMBOLS = [
     "evaluate", "num_residuals", "num_parameters_tangent", "tangent_offset", "covariance", "marginalize", "get_marginal",
     "reprojection_errors", "preintegrate", "triangulate", "time_reproj_jacobian_ms", "reproj_jacobian_bytes", "dense_solve", "plan_info",
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
-    "covariance_requests", "localize_frames", "num_factorizations", "essential_ransac",
+    "covariance_requests", "localize_frames", "num_factorizations", "essential_ransac", "absolute_pose_ransac",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -126,6 +126,9 @@ RANSAC_OK, RANSAC_TOO_FEW, RANSAC_NO_MODEL = 0, 1, 2
 RANSAC_MAX_MATCHES = 65536
 ESSENTIAL_RANSAC_ARGTYPES = [C.c_void_p, C.c_int32, _ip, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int32, C.c_uint64, _bp, _dp, _ip, _ip,
                              _ip, _ip]
+#: bsgpu_absolute_pose_ransac: the typed prototype (status values and the frame-size limit are bsgpu_essential_ransac's)
+ABSOLUTE_POSE_RANSAC_ARGTYPES = [C.c_void_p, C.c_int32, _ip, _dp, _dp, _ip, C.c_double, C.c_double, C.c_int32, C.c_uint64, C.c_int32, _bp,
+                                 _dp, _dp, _dp, _ip, _ip, _ip, _ip]
 
 
 def _ptr(a, typ):

@@ -1228,6 +1228,80 @@ int bsgpu_essential_ransac(bsgpu_ctx* c, int32_t n_sets, const int32_t* match_st
   return BSGPU_OK;
 } catch (...) { return api_exception(c); }
 
+int bsgpu_absolute_pose_ransac(bsgpu_ctx* c, int32_t n_frames, const int32_t* obs_start, const double* pixels, const double* points,
+                               const int32_t* camera, double prob, double threshold_px, int32_t max_iters, uint64_t seed,
+                               int32_t truncate_pixels, uint8_t* mask, double* q_out, double* p_out, double* T_cam_world,
+                               int32_t* n_inliers, int32_t* n_iters, int32_t* best_sample, int32_t* status) try {
+  if (!c) return BSGPU_ERR_INVALID;
+  if (n_frames < 0 || !obs_start || !pixels || !points || !camera || !mask || !q_out || !p_out || !status)
+    return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: null argument");
+  if (!(prob >= 0.0 && prob < 1.0)) return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: prob must lie inside [0, 1)");
+  if (!(threshold_px > 0.0) || max_iters <= 0) return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: threshold_px and max_iters must be positive");
+  if (obs_start[0] != 0) return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: obs_start[0] must be 0");
+  for (int f = 0; f < n_frames; ++f) {
+    if (obs_start[f + 1] < obs_start[f]) return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: obs_start must be non-decreasing");
+    if (camera[f] < 0 || camera[f] >= (int)c->cams.size()) return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: camera index out of range");
+  }
+  for (int f = 0; f < n_frames; ++f)
+    if (obs_start[f + 1] - obs_start[f] > BSGPU_RANSAC_MAX_MATCHES)
+      return fail(c, BSGPU_ERR_UNSUPPORTED, "absolute_pose_ransac: a frame holds more than BSGPU_RANSAC_MAX_MATCHES pairs");
+  if (n_frames == 0) return BSGPU_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // one device buffer: inputs [obs_start | camera | cameras | pixels | points], outputs [per-frame doubles | per-frame ints | mask]
+  std::vector<DevCamera> cams(c->cams.size());
+  for (size_t i = 0; i < cams.size(); ++i) {
+    const bsgpu_camera& hc = c->cams[i];
+    cams[i].fx = hc.fx; cams[i].fy = hc.fy; cams[i].cx = hc.cx; cams[i].cy = hc.cy;
+    std::memcpy(cams[i].R, hc.R_cam_baselink, sizeof(cams[i].R));
+    std::memcpy(cams[i].t, hc.t_cam_baselink, sizeof(cams[i].t));
+  }
+  const size_t n_obs = (size_t)obs_start[n_frames];
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_start = al(sizeof(int32_t) * ((size_t)n_frames + 1)), b_cam = al(sizeof(int32_t) * (size_t)n_frames),
+               b_cams = al(sizeof(DevCamera) * cams.size()), b_pix = al(sizeof(double) * 2 * n_obs), b_pts = al(sizeof(double) * 3 * n_obs);
+  const size_t in_bytes = b_start + b_cam + b_cams + b_pix + b_pts;
+  const size_t out_d = al(sizeof(double) * kP3pOutDoubles * (size_t)n_frames), out_i = al(sizeof(int32_t) * kP3pOutInts * (size_t)n_frames),
+               out_m = al(n_obs);
+  std::vector<char> h_in(in_bytes), h_out(out_d + out_i + out_m);
+  const size_t o_cam = b_start, o_cams = o_cam + b_cam, o_pix = o_cams + b_cams, o_pts = o_pix + b_pix;
+  std::memcpy(h_in.data(), obs_start, sizeof(int32_t) * ((size_t)n_frames + 1));
+  std::memcpy(h_in.data() + o_cam, camera, sizeof(int32_t) * (size_t)n_frames);
+  std::memcpy(h_in.data() + o_cams, cams.data(), sizeof(DevCamera) * cams.size());
+  if (n_obs) {
+    std::memcpy(h_in.data() + o_pix, pixels, sizeof(double) * 2 * n_obs);
+    std::memcpy(h_in.data() + o_pts, points, sizeof(double) * 3 * n_obs);
+  }
+  char* d = nullptr;
+  if (hipMalloc((void**)&d, in_bytes + h_out.size()) != hipSuccess) { (void)hipGetLastError(); return fail(c, BSGPU_ERR_DEVICE, "absolute_pose_ransac: out of device memory"); }
+  hipError_t e = hipMemcpyAsync(d, h_in.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    launch_absolute_pose_ransac(c->stream, n_frames, (const int*)d, (const double2*)(d + o_pix), (const double*)(d + o_pts),
+                                (const DevCamera*)(d + o_cams), (const int*)(d + o_cam), prob, threshold_px, max_iters, seed,
+                                truncate_pixels != 0 ? 1 : 0, (unsigned char*)(d + in_bytes + out_d + out_i), (double*)(d + in_bytes),
+                                (int*)(d + in_bytes + out_d));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d + in_bytes, h_out.size(), hipMemcpyDeviceToHost, c->stream);
+  const hipError_t e2 = hipStreamSynchronize(c->stream);
+  (void)hipFree(d);
+  if (e != hipSuccess || e2 != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "absolute_pose_ransac: device error");
+  const double* od = (const double*)h_out.data();
+  const int32_t* oi = (const int32_t*)(h_out.data() + out_d);
+  if (n_obs) std::memcpy(mask, h_out.data() + out_d + out_i, n_obs);
+  for (int f = 0; f < n_frames; ++f) {
+    const double* r = od + (size_t)kP3pOutDoubles * f;
+    const int32_t* ri = oi + (size_t)kP3pOutInts * f;
+    if (T_cam_world) std::memcpy(T_cam_world + 12 * (size_t)f, r, 12 * sizeof(double));
+    std::memcpy(q_out + 4 * (size_t)f, r + 12, 4 * sizeof(double));
+    std::memcpy(p_out + 3 * (size_t)f, r + 16, 3 * sizeof(double));
+    if (n_inliers) n_inliers[f] = ri[0];
+    if (n_iters) n_iters[f] = ri[1];
+    if (best_sample) std::memcpy(best_sample + 3 * (size_t)f, ri + 2, 3 * sizeof(int32_t));
+    status[f] = ri[5];
+  }
+  return BSGPU_OK;
+} catch (...) { return api_exception(c); }
+
 double bsgpu_time_reproj_jacobian_ms(bsgpu_ctx* c, int32_t reps) {
   if (!c) return -1.0;
   if (finalize(c) != BSGPU_OK || c->vis.n == 0 || reps <= 0) return -1.0;

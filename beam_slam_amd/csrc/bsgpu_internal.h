@@ -556,6 +556,14 @@ constexpr int kRansacOutInts = 8;
 void launch_essential_ransac(hipStream_t s, int n_sets, const int* match_start, const double2* px_prev, const double2* px_cur,
                              const double* K, double prob, double threshold_px, int max_iters, uint64_t seed, unsigned char* mask,
                              double* out_E, int* out_i);
+// P3P RANSAC frame poses (k_p3p.hip, bsgpu_absolute_pose_ransac): one workgroup per frame; pix 2 / pts 3 per pair, cam_of per frame;
+// mask 1 byte per pair, out_d kP3pOutDoubles per frame [T_cam_world 12 | q wxyz | p], out_i kP3pOutInts per frame
+// [n_inliers | n_iters | best_sample 3 | status]
+constexpr int kP3pOutDoubles = 19;
+constexpr int kP3pOutInts = 6;
+void launch_absolute_pose_ransac(hipStream_t s, int n_frames, const int* obs_start, const double2* pix, const double* pts,
+                                 const DevCamera* cams, const int* cam_of, double prob, double threshold_px, int max_iters, uint64_t seed,
+                                 int truncate, unsigned char* mask, double* out_d, int* out_i);
 // device-side flattening of the reprojection factors (k_flatten.hip): 0 = done, 1 = take the host path, < 0 = device error.
 // `res` non-null: the raw table is already on the device, its block columns naming caller slots (SlotMirror, bsgpu_ctx.h)
 struct FlattenResident { const int* idx; const double* consts; const int* loss_kind; const double* loss_a; const int* slot_map; };

@@ -123,6 +123,34 @@ class GpuSolver(capi.Solver):
                      out["best_sample"].ctypes.data_as(_ip), out["status"].ctypes.data_as(_ip)))
         return out
 
+    def absolute_pose_ransac(self, obs_start, pixels, points, camera=0, prob=0.0, threshold_px=5.0, max_iters=100, seed=0,
+                             truncate_pixels=False):
+        """bsgpu_absolute_pose_ransac: beam_cv::AbsolutePoseEstimator::RANSACEstimator(cam, pixels, points, max_iters) for a batch of
+        frames.  Frame f holds pairs [obs_start[f], obs_start[f+1]); pixels (n x 2), points (n x 3, world); camera (per frame, or one
+        for all): index into set_cameras' table.  prob = 0: the fixed loop; prob in (0, 1): early termination.
+        Returns a dict of arrays: mask (n, uint8), q (F x 4, wxyz) / p (F x 3): T_WORLD_BASELINK, localize_frames' q_init / p_init;
+        T_cam_world (F x 3 x 4), n_inliers, n_iters, best_sample (F x 3), status (F).  NaN poses where status is not RANSAC_OK."""
+        import numpy as np
+        os_ = np.ascontiguousarray(obs_start, np.int32)
+        F = os_.size - 1
+        pix = np.ascontiguousarray(pixels, np.float64).reshape(-1, 2)
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        cam = np.ascontiguousarray(np.broadcast_to(np.asarray(camera, np.int32), (F,)))
+        if pix.shape[0] != pts.shape[0] or (os_.size and pix.shape[0] < int(os_.max())):
+            raise capi.SolverError(capi.ERR_INVALID, "absolute_pose_ransac: obs_start names more pairs than were passed")
+        out = dict(mask=np.zeros(pix.shape[0], np.uint8), q=np.zeros((F, 4)), p=np.zeros((F, 3)), T_cam_world=np.zeros((F, 3, 4)),
+                   n_inliers=np.zeros(F, np.int32), n_iters=np.zeros(F, np.int32), best_sample=np.zeros((F, 3), np.int32),
+                   status=np.zeros(F, np.int32))
+        fn = lib().bsgpu_absolute_pose_ransac
+        fn.argtypes = capi.ABSOLUTE_POSE_RANSAC_ARGTYPES
+        _dp, _ip, _bp = capi._dp, capi._ip, capi._bp
+        self._chk(fn(self._ctx, F, os_.ctypes.data_as(_ip), pix.ctypes.data_as(_dp), pts.ctypes.data_as(_dp), cam.ctypes.data_as(_ip),
+                     float(prob), float(threshold_px), int(max_iters), int(seed) & ((1 << 64) - 1), int(bool(truncate_pixels)),
+                     out["mask"].ctypes.data_as(_bp), out["q"].ctypes.data_as(_dp), out["p"].ctypes.data_as(_dp),
+                     out["T_cam_world"].ctypes.data_as(_dp), out["n_inliers"].ctypes.data_as(_ip), out["n_iters"].ctypes.data_as(_ip),
+                     out["best_sample"].ctypes.data_as(_ip), out["status"].ctypes.data_as(_ip)))
+        return out
+
     @staticmethod
     def batch_stats():
         """(windows solved by the batched launches of bsgpu_solve_batch so far in this process, rounds = sets of launches they took)."""

@@ -559,6 +559,48 @@ int bsgpu_essential_ransac(bsgpu_ctx* ctx, int32_t n_sets, const int32_t* match_
                            const double* K, double prob, double threshold_px, int32_t max_iters, uint64_t seed, uint8_t* mask,
                            double* E, int32_t* n_inliers, int32_t* n_iters, int32_t* best_sample, int32_t* status);
 
+/* P3P RANSAC frame poses for a batch of frames — the
+ * beam_cv::AbsolutePoseEstimator::RANSACEstimator(camera_model, pixels, points, 100) call of
+ * bs_models::vision::ComputePathWithVision (bs_models/src/lib/vision/utils.cpp:143-188), which gives every keyframe between the
+ * first and the last image of SLAMInitialization's window its pose from 2D-3D pairs (slam_initialization.cpp:216), and the pose a
+ * frame needs when there is no frame initialiser or after track_lost_: q_out / p_out are bsgpu_localize_frames' q_init / p_init.
+ * [EXT] libbeam is not in the reference checkout: the semantics below are RECALLED and could not be verified (DESIGN.md
+ * "Absolute-pose RANSAC").  Recalled: a fixed loop of max_iterations, a random 3-subset per iteration, up to 4 P3P poses each, inlier =
+ * reprojection distance below a pixel threshold (default 5), the best count wins, no refit.  This library's own choices: the sampler,
+ * the order of a sample's solutions, "strictly greater than max(best, 3)", P_c.z > 0 as part of the inlier test, the optional early
+ * termination (prob > 0), TOO_FEW below 4 pairs, and what a frame without a model returns.
+ *   frame f holds pairs [obs_start[f], obs_start[f+1]) (obs_start[0] == 0, non-decreasing); pixels: 2 per pair, undistorted,
+ *   truncated toward zero when truncate_pixels != 0 (the reference's cast<int>(), utils.cpp:159), for the solve and for the scoring
+ *   alike; points: 3 per pair, world frame; camera: per frame, an index into the bsgpu_set_cameras table (pinhole K, T_cam_baselink).
+ *   Minimal sample: 3 pairs; model: every real P3P solution T_CAMERA_WORLD = [R|t] (at most 4) with all three depths positive, in
+ *   ascending order of the camera-frame depth of the sample's FIRST point; score: P_c = R P + t, inlier iff P_c.z > 0 and
+ *   (fx x/z + cx - u)^2 + (fy y/z + cy - v)^2 < threshold_px^2, every multiply-add a fused one.  Loop: niters = max_iters; for sample
+ *   s = 0, 1, ... while s < niters, every solution of sample s whose inlier count is strictly greater than max(best, 3) becomes the
+ *   best and, when prob lies inside (0, 1), sets niters = update(prob, (n - good) / n, 3, niters) [num = log(1 - prob),
+ *   den = log(1 - (1 - ep)^3); niters when den >= 0 or -num >= niters * -den, otherwise round(num / den); 0 when ep == 0].
+ *   prob == 0: no early termination — the libbeam loop as recalled; max_iters = 100 is the reference's call.  No refit; the mask is
+ *   the best model's inlier set.
+ *   Sampler (part of the contract, all arithmetic mod 2^64): state = seed ^ (k * 0x9E3779B97F4A7C15) ^ (s * 0xBF58476D1CE4E5B9) with
+ *   k the frame's position in THIS call; three distinct indices by the draw and redraw rule of bsgpu_essential_ransac (splitmix64,
+ *   index = z mod n, a draw equal to an earlier index of the same sample is drawn again).  A sample without a solution counts as an
+ *   iteration.
+ * Outputs: mask (1 per pair: 1 = inlier of the best model); q_out (4 per frame, wxyz, unit, w >= 0) / p_out (3 per frame):
+ * T_WORLD_BASELINK = T_CAMERA_WORLD^-1 T_cam_baselink (visual_odometry.cpp:252-253); T_cam_world (12 per frame, row-major [R|t], may
+ * be NULL); n_inliers, n_iters (samples the loop consumed), best_sample (3 per frame: the winning sample's pair indices inside the
+ * frame) — each may be NULL; status per frame: BSGPU_RANSAC_OK; BSGPU_RANSAC_TOO_FEW (fewer than 4 pairs — three cannot tell P3P's
+ * solutions apart: n_iters 0); BSGPU_RANSAC_NO_MODEL (no solution ever reached 4 inliers).  In both of those the mask is all 0,
+ * n_inliers 0, best_sample -1 and every pose output NaN: a frame without a model has no pose (a decision of this library; libbeam's
+ * behaviour there is not verifiable here).
+ * A frame's results do not depend on the other frames of the call except through its position k.  The context needs cameras only: it
+ * need not be finalized and is not changed.  INVALID: a NULL ctx / obs_start / pixels / points / camera / mask / q_out / p_out /
+ * status, n_frames < 0, a malformed obs_start, a camera index outside the table, prob outside [0, 1) or NaN, threshold_px <= 0,
+ * max_iters <= 0.  UNSUPPORTED: a frame of more than BSGPU_RANSAC_MAX_MATCHES pairs.  Nothing is written on an argument error.   */
+int bsgpu_absolute_pose_ransac(bsgpu_ctx* ctx, int32_t n_frames, const int32_t* obs_start, const double* pixels,
+                               const double* points, const int32_t* camera, double prob, double threshold_px,
+                               int32_t max_iters, uint64_t seed, int32_t truncate_pixels, uint8_t* mask,
+                               double* q_out, double* p_out, double* T_cam_world, int32_t* n_inliers,
+                               int32_t* n_iters, int32_t* best_sample, int32_t* status);
+
 /* ---- measurement helpers (used by bench.py only) --------------------------- */
 /* Launches the Jacobian-evaluation kernel of the reprojection factors `reps`
  * times on the context's stream between two HIP events and returns the average
