@@ -115,6 +115,7 @@ SYMBOLS = [
     "reprojection_errors", "preintegrate", "triangulate", "time_reproj_jacobian_ms", "reproj_jacobian_bytes", "dense_solve", "plan_info",
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
     "covariance_requests", "localize_frames", "num_factorizations", "essential_ransac", "absolute_pose_ransac",
+    "relative_pose_ransac",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -129,6 +130,9 @@ ESSENTIAL_RANSAC_ARGTYPES = [C.c_void_p, C.c_int32, _ip, _dp, _dp, _dp, C.c_doub
 #: bsgpu_absolute_pose_ransac: the typed prototype (status values and the frame-size limit are bsgpu_essential_ransac's)
 ABSOLUTE_POSE_RANSAC_ARGTYPES = [C.c_void_p, C.c_int32, _ip, _dp, _dp, _ip, C.c_double, C.c_double, C.c_int32, C.c_uint64, C.c_int32, _bp,
                                  _dp, _dp, _dp, _ip, _ip, _ip, _ip]
+#: bsgpu_relative_pose_ransac: the typed prototype (status values and the set-size limit are bsgpu_essential_ransac's)
+RELATIVE_POSE_RANSAC_ARGTYPES = [C.c_void_p, C.c_int32, _ip, _dp, _dp, _ip, C.c_double, C.c_double, C.c_int32, C.c_uint64, C.c_int32,
+                                 C.c_double, C.c_double, _bp, _dp, _dp, _dp, _dp, _bp, _dp, _ip, _ip, _ip, _ip, _ip]
 
 
 def _ptr(a, typ):

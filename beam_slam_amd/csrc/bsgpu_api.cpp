@@ -1302,6 +1302,92 @@ int bsgpu_absolute_pose_ransac(bsgpu_ctx* c, int32_t n_frames, const int32_t* ob
   return BSGPU_OK;
 } catch (...) { return api_exception(c); }
 
+int bsgpu_relative_pose_ransac(bsgpu_ctx* c, int32_t n_sets, const int32_t* match_start, const double* px_first, const double* px_last,
+                               const int32_t* camera, double prob, double threshold_px, int32_t max_iters, uint64_t seed,
+                               int32_t truncate_pixels, double validate_px, double min_inlier_ratio, uint8_t* mask, double* T_last_first,
+                               double* q_out, double* p_out, double* points, uint8_t* valid_mask, double* inlier_ratio,
+                               int32_t* pair_valid, int32_t* n_inliers, int32_t* n_iters, int32_t* best_sample, int32_t* status) try {
+  if (!c) return BSGPU_ERR_INVALID;
+  if (n_sets < 0 || !match_start || !px_first || !px_last || !camera || !mask || !q_out || !p_out || !pair_valid || !status)
+    return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: null argument");
+  if (!(prob >= 0.0 && prob < 1.0)) return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: prob must lie inside [0, 1)");
+  if (!(threshold_px > 0.0) || !(validate_px > 0.0) || max_iters <= 0)
+    return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: threshold_px, validate_px and max_iters must be positive");
+  if (!(min_inlier_ratio >= 0.0 && min_inlier_ratio <= 1.0)) return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: min_inlier_ratio must lie inside [0, 1]");
+  if (match_start[0] != 0) return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: match_start[0] must be 0");
+  for (int k = 0; k < n_sets; ++k) {
+    if (match_start[k + 1] < match_start[k]) return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: match_start must be non-decreasing");
+    if (camera[k] < 0 || camera[k] >= (int)c->cams.size()) return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: camera index out of range");
+  }
+  for (int k = 0; k < n_sets; ++k)
+    if (match_start[k + 1] - match_start[k] > BSGPU_RANSAC_MAX_MATCHES)
+      return fail(c, BSGPU_ERR_UNSUPPORTED, "relative_pose_ransac: a set holds more than BSGPU_RANSAC_MAX_MATCHES matches");
+  if (n_sets == 0) return BSGPU_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  // one device buffer: inputs [match_start | camera | cameras | px_first | px_last], outputs [per-set doubles | per-set ints | points |
+  // mask | valid_mask]
+  std::vector<DevCamera> cams(c->cams.size());
+  for (size_t i = 0; i < cams.size(); ++i) {
+    const bsgpu_camera& hc = c->cams[i];
+    cams[i].fx = hc.fx; cams[i].fy = hc.fy; cams[i].cx = hc.cx; cams[i].cy = hc.cy;
+    std::memcpy(cams[i].R, hc.R_cam_baselink, sizeof(cams[i].R));
+    std::memcpy(cams[i].t, hc.t_cam_baselink, sizeof(cams[i].t));
+  }
+  const size_t n_m = (size_t)match_start[n_sets];
+  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t b_start = al(sizeof(int32_t) * ((size_t)n_sets + 1)), b_cam = al(sizeof(int32_t) * (size_t)n_sets),
+               b_cams = al(sizeof(DevCamera) * cams.size()), b_px = al(sizeof(double) * 2 * n_m);
+  const size_t in_bytes = b_start + b_cam + b_cams + 2 * b_px;
+  const size_t out_d = al(sizeof(double) * kRelposeOutDoubles * (size_t)n_sets), out_i = al(sizeof(int32_t) * kRelposeOutInts * (size_t)n_sets),
+               out_p = al(sizeof(double) * 3 * n_m), out_m = al(n_m);
+  std::vector<char> h_in(in_bytes), h_out(out_d + out_i + out_p + 2 * out_m);
+  const size_t o_cam = b_start, o_cams = o_cam + b_cam, o_p0 = o_cams + b_cams, o_p1 = o_p0 + b_px;
+  std::memcpy(h_in.data(), match_start, sizeof(int32_t) * ((size_t)n_sets + 1));
+  std::memcpy(h_in.data() + o_cam, camera, sizeof(int32_t) * (size_t)n_sets);
+  std::memcpy(h_in.data() + o_cams, cams.data(), sizeof(DevCamera) * cams.size());
+  if (n_m) {
+    std::memcpy(h_in.data() + o_p0, px_first, sizeof(double) * 2 * n_m);
+    std::memcpy(h_in.data() + o_p1, px_last, sizeof(double) * 2 * n_m);
+  }
+  char* d = nullptr;
+  if (hipMalloc((void**)&d, in_bytes + h_out.size()) != hipSuccess) { (void)hipGetLastError(); return fail(c, BSGPU_ERR_DEVICE, "relative_pose_ransac: out of device memory"); }
+  char* dout = d + in_bytes;
+  hipError_t e = hipMemcpyAsync(d, h_in.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) {
+    launch_relative_pose_ransac(c->stream, n_sets, (const int*)d, (const double2*)(d + o_p0), (const double2*)(d + o_p1),
+                                (const DevCamera*)(d + o_cams), (const int*)(d + o_cam), prob, threshold_px, max_iters, seed,
+                                truncate_pixels != 0 ? 1 : 0, validate_px, min_inlier_ratio, (unsigned char*)(dout + out_d + out_i + out_p),
+                                (unsigned char*)(dout + out_d + out_i + out_p + out_m), (double*)(dout + out_d + out_i), (double*)dout,
+                                (int*)(dout + out_d));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), dout, h_out.size(), hipMemcpyDeviceToHost, c->stream);
+  const hipError_t e2 = hipStreamSynchronize(c->stream);
+  (void)hipFree(d);
+  if (e != hipSuccess || e2 != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "relative_pose_ransac: device error");
+  const double* od = (const double*)h_out.data();
+  const int32_t* oi = (const int32_t*)(h_out.data() + out_d);
+  if (n_m) {
+    std::memcpy(mask, h_out.data() + out_d + out_i + out_p, n_m);
+    if (valid_mask) std::memcpy(valid_mask, h_out.data() + out_d + out_i + out_p + out_m, n_m);
+    if (points) std::memcpy(points, h_out.data() + out_d + out_i, sizeof(double) * 3 * n_m);
+  }
+  for (int k = 0; k < n_sets; ++k) {
+    const double* r = od + (size_t)kRelposeOutDoubles * k;
+    const int32_t* ri = oi + (size_t)kRelposeOutInts * k;
+    if (T_last_first) std::memcpy(T_last_first + 12 * (size_t)k, r, 12 * sizeof(double));
+    std::memcpy(q_out + 8 * (size_t)k, r + 12, 8 * sizeof(double));
+    std::memcpy(p_out + 6 * (size_t)k, r + 20, 6 * sizeof(double));
+    if (inlier_ratio) inlier_ratio[k] = r[26];
+    if (n_inliers) n_inliers[k] = ri[0];
+    if (n_iters) n_iters[k] = ri[1];
+    if (best_sample) std::memcpy(best_sample + 7 * (size_t)k, ri + 2, 7 * sizeof(int32_t));
+    status[k] = ri[9];
+    pair_valid[k] = ri[10];
+  }
+  return BSGPU_OK;
+} catch (...) { return api_exception(c); }
+
 double bsgpu_time_reproj_jacobian_ms(bsgpu_ctx* c, int32_t reps) {
   if (!c) return -1.0;
   if (finalize(c) != BSGPU_OK || c->vis.n == 0 || reps <= 0) return -1.0;

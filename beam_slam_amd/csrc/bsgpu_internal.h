@@ -564,6 +564,16 @@ constexpr int kP3pOutInts = 6;
 void launch_absolute_pose_ransac(hipStream_t s, int n_frames, const int* obs_start, const double2* pix, const double* pts,
                                  const DevCamera* cams, const int* cam_of, double prob, double threshold_px, int max_iters, uint64_t seed,
                                  int truncate, unsigned char* mask, double* out_d, int* out_i);
+// seven-point RANSAC two-view bootstrap (k_relpose.hip, bsgpu_relative_pose_ransac): one workgroup per match set; pixels 2 per match,
+// cam_of per set; mask / valid_mask 1 byte per match, points 3 per match, out_d kRelposeOutDoubles per set
+// [T_last_first 12 | q wxyz first, last | p first, last | inlier_ratio], out_i kRelposeOutInts per set
+// [n_inliers | n_iters | best_sample 7 | status | pair_valid]
+constexpr int kRelposeOutDoubles = 27;
+constexpr int kRelposeOutInts = 11;
+void launch_relative_pose_ransac(hipStream_t s, int n_sets, const int* match_start, const double2* pix_first, const double2* pix_last,
+                                 const DevCamera* cams, const int* cam_of, double prob, double threshold_px, int max_iters, uint64_t seed,
+                                 int truncate, double validate_px, double min_inlier_ratio, unsigned char* mask, unsigned char* valid_mask,
+                                 double* points, double* out_d, int* out_i);
 // device-side flattening of the reprojection factors (k_flatten.hip): 0 = done, 1 = take the host path, < 0 = device error.
 // `res` non-null: the raw table is already on the device, its block columns naming caller slots (SlotMirror, bsgpu_ctx.h)
 struct FlattenResident { const int* idx; const double* consts; const int* loss_kind; const double* loss_a; const int* slot_map; };

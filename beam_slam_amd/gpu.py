@@ -151,6 +151,40 @@ class GpuSolver(capi.Solver):
                      out["best_sample"].ctypes.data_as(_ip), out["status"].ctypes.data_as(_ip)))
         return out
 
+    def relative_pose_ransac(self, match_start, px_first, px_last, camera=0, prob=0.0, threshold_px=5.0, max_iters=100, seed=0,
+                             truncate_pixels=False, validate_px=10.0, min_inlier_ratio=0.8):
+        """bsgpu_relative_pose_ransac: the two-view bootstrap of ComputePathWithVision — seven-point RANSAC relative pose of the last
+        image against the first, triangulation of every match and the validity gate — for a batch of match sets.  Set k holds matches
+        [match_start[k], match_start[k+1]); px_first / px_last (n x 2) pixels; camera (per set, or one for all): index into
+        set_cameras' table.  prob = 0: the fixed loop; prob in (0, 1): early termination.
+        Returns a dict of arrays: mask (n, uint8), T_last_first (S x 3 x 4), q (S x 2 x 4, wxyz) / p (S x 2 x 3): T_WORLD_BASELINK of
+        the first and the last image (world = first camera), points (n x 3, first camera's frame), valid_mask (n, uint8),
+        inlier_ratio, pair_valid, n_inliers, n_iters, best_sample (S x 7), status (S).  NaN where status is not RANSAC_OK."""
+        import numpy as np
+        ms = np.ascontiguousarray(match_start, np.int32)
+        S = ms.size - 1
+        p0 = np.ascontiguousarray(px_first, np.float64).reshape(-1, 2)
+        p1 = np.ascontiguousarray(px_last, np.float64).reshape(-1, 2)
+        cam = np.ascontiguousarray(np.broadcast_to(np.asarray(camera, np.int32), (S,)))
+        if p0.shape != p1.shape or (ms.size and p0.shape[0] < int(ms.max())):
+            raise capi.SolverError(capi.ERR_INVALID, "relative_pose_ransac: match_start names more matches than were passed")
+        n = p0.shape[0]
+        out = dict(mask=np.zeros(n, np.uint8), T_last_first=np.zeros((S, 3, 4)), q=np.zeros((S, 2, 4)), p=np.zeros((S, 2, 3)),
+                   points=np.zeros((n, 3)), valid_mask=np.zeros(n, np.uint8), inlier_ratio=np.zeros(S), pair_valid=np.zeros(S, np.int32),
+                   n_inliers=np.zeros(S, np.int32), n_iters=np.zeros(S, np.int32), best_sample=np.zeros((S, 7), np.int32),
+                   status=np.zeros(S, np.int32))
+        fn = lib().bsgpu_relative_pose_ransac
+        fn.argtypes = capi.RELATIVE_POSE_RANSAC_ARGTYPES
+        _dp, _ip, _bp = capi._dp, capi._ip, capi._bp
+        self._chk(fn(self._ctx, S, ms.ctypes.data_as(_ip), p0.ctypes.data_as(_dp), p1.ctypes.data_as(_dp), cam.ctypes.data_as(_ip),
+                     float(prob), float(threshold_px), int(max_iters), int(seed) & ((1 << 64) - 1), int(bool(truncate_pixels)),
+                     float(validate_px), float(min_inlier_ratio), out["mask"].ctypes.data_as(_bp), out["T_last_first"].ctypes.data_as(_dp),
+                     out["q"].ctypes.data_as(_dp), out["p"].ctypes.data_as(_dp), out["points"].ctypes.data_as(_dp),
+                     out["valid_mask"].ctypes.data_as(_bp), out["inlier_ratio"].ctypes.data_as(_dp), out["pair_valid"].ctypes.data_as(_ip),
+                     out["n_inliers"].ctypes.data_as(_ip), out["n_iters"].ctypes.data_as(_ip), out["best_sample"].ctypes.data_as(_ip),
+                     out["status"].ctypes.data_as(_ip)))
+        return out
+
     @staticmethod
     def batch_stats():
         """(windows solved by the batched launches of bsgpu_solve_batch so far in this process, rounds = sets of launches they took)."""

@@ -601,6 +601,65 @@ int bsgpu_absolute_pose_ransac(bsgpu_ctx* ctx, int32_t n_frames, const int32_t* 
                                double* q_out, double* p_out, double* T_cam_world, int32_t* n_inliers,
                                int32_t* n_iters, int32_t* best_sample, int32_t* status);
 
+/* Seven-point RANSAC two-view bootstrap for a batch of match sets — steps 1 and 2 of bs_models::vision::ComputePathWithVision
+ * (bs_models/src/lib/vision/utils.cpp:44-94, called from slam_initialization.cpp:216): the relative pose of the last image of the
+ * window against the first, beam_cv::RelativePoseEstimator::RANSACEstimator(cam, cam, first, last, SEVENPOINT, 100), the two-view
+ * triangulation of every match, Triangulation::TriangulatePoints, and the 10 px / 80 % validity gate.  Together with
+ * bsgpu_absolute_pose_ransac (step 3) and bsgpu_solve (step 4) the bootstrap stays on the device; `points` at valid_mask are the
+ * world points step 3 takes.
+ * [EXT] libbeam is not in the reference checkout: the semantics below are RECALLED and could not be verified (DESIGN.md
+ * "Relative-pose RANSAC").  Recalled: a fixed loop of max_iterations, a random 7-subset per iteration, the seven-point solver's one
+ * or three matrices, each decomposed into its four poses, every pose scored by triangulating every match and reprojecting it into
+ * both images against a pixel threshold (default 5), the best count wins, no refit.  This library's own choices: the sampler, the
+ * order of a sample's matrices and of a matrix' four poses, "strictly greater than max(best, 7)", positive depth in both cameras as
+ * part of the inlier test, the optional early termination (prob > 0), TOO_FEW below 8 matches, and what a set without a model
+ * returns.
+ *   set k holds matches [match_start[k], match_start[k+1]) (match_start[0] == 0, non-decreasing); px_first / px_last: 2 per match,
+ *   undistorted pixels of the first and the last image, truncated toward zero when truncate_pixels != 0 (the reference's
+ *   cast<int>(), utils.cpp:34-36) — for the solve, the scoring, the triangulation and the gate alike; camera: per set, an index into
+ *   the bsgpu_set_cameras table; the one pinhole camera serves both images (the reference passes camera_model twice).  Normalised
+ *   coordinates are x = ((u - cx) / fx, (v - cy) / fy).
+ *   Minimal sample: 7 distinct matches.  Models: every real E of the two-dimensional null space of the 7 x 9 system
+ *   x_last^T E x_first = 0 with det E = 0 (one or three), scaled to |E|_F = 1 with its largest-magnitude entry positive, in ascending
+ *   order of E[0] (the five-point rule).  Each E = U diag(s) V^T (U, V proper rotations) gives four poses T_last_first = [R|t],
+ *   R in {U W V^T, U W^T V^T}, t = +-u3, in the order (R_a, +t), (R_a, -t), (R_b, +t), (R_b, -t): R_a the rotation with the larger
+ *   trace, +t the unit left null vector with its largest-magnitude component positive.  All four are hypotheses.
+ *   Triangulation: bsgpu_triangulate's definition for the two views [I|0] and [R|t] — unit bearings, four DLT rows, the right
+ *   singular vector of the smallest singular value, de-homogenised; homogeneous w == 0 is the point at infinity (its status 5).
+ *   Inlier iff the point is finite, its depth is positive in both cameras and the squared reprojection distance is below
+ *   threshold_px^2 in BOTH images, every multiply-add of the test a fused one.
+ *   Loop: niters = max_iters; for sample s = 0, 1, ... while s < niters, every hypothesis of sample s, in the order above, whose
+ *   inlier count is strictly greater than max(best, 7) becomes the best and, when prob lies inside (0, 1), sets
+ *   niters = update(prob, (n - good) / n, 7, niters) [bsgpu_absolute_pose_ransac's rule with exponent 7].  prob == 0: no early
+ *   termination — the libbeam loop as recalled; max_iters = 100, threshold_px = 5 (libbeam's default as recalled) is the reference's
+ *   call.  No refit.  A sample without a model counts as an iteration.
+ *   Sampler (part of the contract): state = seed ^ (k * 0x9E3779B97F4A7C15) ^ (s * 0xBF58476D1CE4E5B9) with k the set's position in
+ *   THIS call; seven distinct indices by the draw and redraw rule of bsgpu_essential_ransac.
+ *   After the loop (utils.cpp:57-94): points (3 per match) in the first camera's frame — the reference's world — triangulated under
+ *   the best model, NaN for a point at infinity; valid_mask[i] = 1 iff the point is in front of both cameras and both reprojection
+ *   distances are below validate_px (the reference: 10); inlier_ratio = sum(valid_mask) / n in double (the reference's total_size is
+ *   decremented but never read); pair_valid = !(inlier_ratio < min_inlier_ratio) (the reference: 0.8; it compares a float ratio —
+ *   for n <= 65 536 = BSGPU_RANSAC_MAX_MATCHES the two comparisons agree).
+ * Outputs: mask (1 per match: 1 = inlier of the best model); T_last_first (12 per set, row-major [R|t], |t| = 1, may be NULL);
+ * q_out (8 per set) / p_out (6 per set): TWO poses per set, T_WORLD_BASELINK of the first and then of the last image with
+ * world = first camera (AddCameraPose, utils.cpp:108-109): T_cam_baselink and T_last_first^-1 T_cam_baselink, each wxyz with w >= 0
+ * and xyz, as bsgpu_localize_frames takes them; points, valid_mask, inlier_ratio (may be NULL); pair_valid (1 per set); n_inliers,
+ * n_iters (samples the loop consumed), best_sample (7 per set) — each may be NULL; status per set: BSGPU_RANSAC_OK;
+ * BSGPU_RANSAC_TOO_FEW (fewer than 8 matches — seven always fit their own model: n_iters 0); BSGPU_RANSAC_NO_MODEL (no hypothesis
+ * ever reached 8 inliers).  In both of those both masks are 0, the counts 0, best_sample -1, pair_valid 0 and every pose, point and
+ * ratio NaN (a decision of this library; libbeam's behaviour there is not verifiable here).
+ * A set's results do not depend on the other sets of the call except through its position k.  The context needs cameras only: it
+ * need not be finalized and is not changed.  INVALID: a NULL ctx / match_start / px_first / px_last / camera / mask / q_out / p_out /
+ * pair_valid / status, n_sets < 0, a malformed match_start, a camera index outside the table, prob outside [0, 1) or NaN,
+ * threshold_px <= 0, validate_px <= 0, max_iters <= 0, min_inlier_ratio outside [0, 1].  UNSUPPORTED: a set of more than
+ * BSGPU_RANSAC_MAX_MATCHES matches.  Nothing is written on an argument error.                                                       */
+int bsgpu_relative_pose_ransac(bsgpu_ctx* ctx, int32_t n_sets, const int32_t* match_start, const double* px_first,
+                               const double* px_last, const int32_t* camera, double prob, double threshold_px,
+                               int32_t max_iters, uint64_t seed, int32_t truncate_pixels, double validate_px,
+                               double min_inlier_ratio, uint8_t* mask, double* T_last_first, double* q_out, double* p_out,
+                               double* points, uint8_t* valid_mask, double* inlier_ratio, int32_t* pair_valid,
+                               int32_t* n_inliers, int32_t* n_iters, int32_t* best_sample, int32_t* status);
+
 /* ---- measurement helpers (used by bench.py only) --------------------------- */
 /* Launches the Jacobian-evaluation kernel of the reprojection factors `reps`
  * times on the context's stream between two HIP events and returns the average
