@@ -992,10 +992,15 @@ int bsgpu_reprojection_errors(bsgpu_ctx* c, double* err) try {
 int bsgpu_preintegrate(int device, int32_t n, const int32_t* sample_start, const double* t, const double* w, const double* a,
                        const double* t_end, const double* bg, const double* ba, const double* cov_w, const double* cov_a,
                        const double* cov_bg, const double* cov_ba, double info_weight, double* consts_out) try {
-  if (n <= 0 || !sample_start || !t || !w || !a || !t_end || !bg || !ba || !cov_w || !cov_a || !cov_bg || !cov_ba || !consts_out) return BSGPU_ERR_INVALID;
-  if (hipSetDevice(device) != hipSuccess) return BSGPU_ERR_DEVICE;
+  if (n < 0) return BSGPU_ERR_INVALID;
+  if (n == 0) return BSGPU_OK;
+  if (!sample_start || !t_end || !bg || !ba || !cov_w || !cov_a || !cov_bg || !cov_ba || !consts_out) return BSGPU_ERR_INVALID;
+  // an interval may hold no samples (it stays the identity); the kernel indexes the samples by this table, so it is checked here
+  if (sample_start[0] < 0) return BSGPU_ERR_INVALID;
+  for (int i = 0; i < n; ++i) if (sample_start[i + 1] < sample_start[i]) return BSGPU_ERR_INVALID;
   const int ns = sample_start[n];
-  if (ns <= 0) return BSGPU_ERR_INVALID;
+  if (ns > 0 && (!t || !w || !a)) return BSGPU_ERR_INVALID;
+  if (hipSetDevice(device) != hipSuccess) return BSGPU_ERR_DEVICE;
   std::vector<double> covs(36);
   std::memcpy(&covs[0], cov_w, 72); std::memcpy(&covs[9], cov_a, 72); std::memcpy(&covs[18], cov_bg, 72); std::memcpy(&covs[27], cov_ba, 72);
   std::vector<void*> bufs;
@@ -1007,9 +1012,9 @@ int bsgpu_preintegrate(int device, int32_t n, const int32_t* sample_start, const
     return d;
   };
   int* d_ss = (int*)up(sample_start, sizeof(int) * (n + 1));
-  double* d_t = (double*)up(t, sizeof(double) * ns);
-  double* d_w = (double*)up(w, sizeof(double) * 3 * ns);
-  double* d_a = (double*)up(a, sizeof(double) * 3 * ns);
+  double* d_t = (double*)up(ns ? t : nullptr, sizeof(double) * (ns ? ns : 1));
+  double* d_w = (double*)up(ns ? w : nullptr, sizeof(double) * 3 * (ns ? ns : 1));
+  double* d_a = (double*)up(ns ? a : nullptr, sizeof(double) * 3 * (ns ? ns : 1));
   double* d_te = (double*)up(t_end, sizeof(double) * n);
   double* d_bg = (double*)up(bg, sizeof(double) * 3 * n);
   double* d_ba = (double*)up(ba, sizeof(double) * 3 * n);

@@ -22,6 +22,8 @@
 // Every E gives four poses T_last_first = [R|t] from E = U diag(s) V^T (sp7_decompose), in the canonical order of the contract.
 // A match is scored by triangulating it (sp7_triangulate: bsgpu_triangulate's DLT for the views [I|0] and [R|t], the 4 x 4 Gram
 // matrix diagonalised by cyclic Jacobi with compile-time indices) and reprojecting the point into both images (sp7_inlier).
+// (bsgpu_triangulate's definition, not its method: in the first camera's frame with a unit baseline A is well conditioned and the
+// Gram matrix loses nothing that matters; bsgpu_triangulate works in world coordinates and takes the singular vector from A.)
 #pragma once
 #include <cmath>
 #include <cstdint>
@@ -325,7 +327,9 @@ BSG_SP7_FN void sp7_jacobi(double a[4][4], double v[4][4]) {
   }
 }
 
-// bsgpu_triangulate's definition for the views [I|0] and T = [R|t]: unit bearings of the normalised coordinates (x1, y1), (x2, y2),
+// bsgpu_triangulate's definition (what is computed; triangulate_core.h computes it without the Gram matrix, which far from the
+// world origin squares a large condition number — here the frame is the first camera's and the baseline 1) for the views [I|0] and
+// T = [R|t]: unit bearings of the normalised coordinates (x1, y1), (x2, y2),
 // four DLT rows, the right singular vector of the smallest singular value (the eigenvector of the smallest eigenvalue of the Gram
 // matrix), de-homogenised.  false: the point at infinity (homogeneous w == 0, bsgpu_triangulate's status 5); P is then NaN.
 // The sweeps stop once the off-diagonal mass is below 1e-20 of the trace: Jacobi converges quadratically, so the eigenvectors are

@@ -472,7 +472,9 @@ int bsgpu_reprojection_errors(bsgpu_ctx* ctx, double* err);
 /* bs_common::PreIntegrator::Integrate (bs_common/src/bs_common/preintegrator.cpp:26-143) for a batch of keyframe
  * intervals on the device: interval i integrates samples [sample_start[i], sample_start[i+1]) (time-ordered,
  * t / gyro w[3] / accel a[3] per sample) up to t_end[i] with the bias estimates bg[3i..], ba[3i..], and the
- * continuous-time noise covariances cov_w, cov_a, cov_bg, cov_ba (3x3 row-major each).
+ * continuous-time noise covariances cov_w, cov_a, cov_bg, cov_ba (3x3 row-major each).  An interval may hold no
+ * samples (zero delta, the guards' covariances); n_intervals == 0 does nothing.  sample_start must be non-negative
+ * and non-decreasing (else INVALID).
  * consts_out: n_intervals x 287 doubles — the constant payload of BSGPU_F_IMU_DELTA (dt, dq, dp, dv, bias
  * Jacobians, bias linearisation point, A = info_weight * sqrt_inv_cov), ready for bsgpu_add_factors.           */
 int bsgpu_preintegrate(int device, int32_t n_intervals, const int32_t* sample_start, const double* t, const double* w,

@@ -1,8 +1,10 @@
 """Landmark triangulation — the factor producer of SURVEY.md §8f rank 4.
 CPU: the numpy restatement (oracle/triangulation.py) recovers known points and honours the call contract of
 bs_models/src/visual_odometry.cpp:532-610.  GPU: bsgpu_triangulate against that restatement on the tracks of a VIO window.
-Tolerance: 1e-7 relative on the coordinates — the device takes the smallest eigenvector of A^T A (4x4, in registers), the
-restatement the singular vector of A; the two agree to ~cond(A) * 1e-16."""
+Tolerance: 1e-7 relative on the coordinates.  Both sides take the right singular vector of A itself (the device by a QR of the rows
+and Jacobi, the restatement by LAPACK), so they agree to ~cond(A) * 1e-16; the smallest eigenvector of A^T A, which the device used
+to take, is only good to ~cond(A)^2 * 1e-16, which this window at the world origin could not show.  tests/test_triangulation_hp.py
+holds the kernel to a 50-digit reference away from the origin."""
 import os
 import sys
 
