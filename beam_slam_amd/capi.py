@@ -115,7 +115,7 @@ SYMBOLS = [
     "reprojection_errors", "preintegrate", "triangulate", "time_reproj_jacobian_ms", "reproj_jacobian_bytes", "dense_solve", "plan_info",
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
     "covariance_requests", "localize_frames", "num_factorizations", "essential_ransac", "absolute_pose_ransac",
-    "relative_pose_ransac",
+    "relative_pose_ransac", "inertial_alignment",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -133,6 +133,12 @@ ABSOLUTE_POSE_RANSAC_ARGTYPES = [C.c_void_p, C.c_int32, _ip, _dp, _dp, _ip, C.c_
 #: bsgpu_relative_pose_ransac: the typed prototype (status values and the set-size limit are bsgpu_essential_ransac's)
 RELATIVE_POSE_RANSAC_ARGTYPES = [C.c_void_p, C.c_int32, _ip, _dp, _dp, _ip, C.c_double, C.c_double, C.c_int32, C.c_uint64, C.c_int32,
                                  C.c_double, C.c_double, _bp, _dp, _dp, _dp, _dp, _bp, _dp, _ip, _ip, _ip, _ip, _ip]
+#: bsgpu_inertial_alignment: per-path status values, the reference's parameters (inertial_alignment.cpp:84, slam_initialization.cpp:313)
+#: and the typed prototype
+ALIGN_OK, ALIGN_TOO_FEW_FRAMES, ALIGN_BAD_IMU, ALIGN_NOT_EXCITED, ALIGN_RANK_DEFICIENT, ALIGN_SCALE_REJECTED = 0, 1, 2, 3, 4, 5
+ALIGN_MIN_EXCITATION, ALIGN_SCALE_MIN, ALIGN_SCALE_MAX, ALIGN_RANK_TOL = 0.25, 0.02, 1.0, 1e-10
+INERTIAL_ALIGNMENT_ARGTYPES = [C.c_int, C.c_int32, _ip, _dp, _dp, _dp, _ip, _dp, _dp, _dp, C.c_int32, C.c_double, C.c_int32, C.c_double,
+                               C.c_double, C.c_double, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _ip]
 
 
 def _ptr(a, typ):

@@ -10,6 +10,7 @@
 
 #include "bsgpu_ctx.h"
 #include "bsgpu_env.h"
+#include "inertial_align.h"
 
 using namespace bsg;
 
@@ -1029,6 +1030,59 @@ int bsgpu_preintegrate(int device, int32_t n, const int32_t* sample_start, const
   }
   for (void* p : bufs) (void)hipFree(p);
   return rc;
+} catch (...) { return api_exception(nullptr); }
+
+int bsgpu_inertial_alignment(int device, int32_t n_paths, const int32_t* frame_start, const double* t_frame, const double* q_frame,
+                             const double* p_frame, const int32_t* imu_range, const double* t, const double* w, const double* a,
+                             int32_t bridge_gap, double min_excitation, int32_t apply_scale, double scale_min, double scale_max,
+                             double rank_tol, double* gravity, double* bg, double* scale, double* excitation, int32_t* gyro_rank,
+                             double* velocity, double* q_out, double* p_out, double* v_out, int32_t* status) try {
+  if (n_paths < 0) return BSGPU_ERR_INVALID;
+  if (n_paths == 0) return BSGPU_OK;
+  if (!frame_start || !imu_range || !gravity || !bg || !scale || !excitation || !gyro_rank || !status) return BSGPU_ERR_INVALID;
+  if (frame_start[0] != 0) return BSGPU_ERR_INVALID;
+  int ns = 0;
+  for (int k = 0; k < n_paths; ++k) {
+    if (frame_start[k + 1] < frame_start[k]) return BSGPU_ERR_INVALID;
+    if (imu_range[2 * k] < 0 || imu_range[2 * k + 1] < imu_range[2 * k]) return BSGPU_ERR_INVALID;
+    ns = std::max(ns, (int)imu_range[2 * k + 1]);
+  }
+  const size_t nf = (size_t)frame_start[n_paths], np = (size_t)n_paths;
+  if (nf > 0 && (!t_frame || !q_frame || !p_frame || !velocity || !q_out || !p_out || !v_out)) return BSGPU_ERR_INVALID;
+  if (ns > 0 && (!t || !w || !a)) return BSGPU_ERR_INVALID;
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return BSGPU_ERR_DEVICE; }
+  // one allocation: [inputs | outputs | scratch], every segment on a 256-byte boundary; one copy in, one copy out
+  struct Seg { const void* src; void* dst; size_t bytes, off; };
+  size_t total = 0;
+  auto seg = [&](const void* src, void* dst, size_t bytes) { Seg s{src, dst, bytes, total}; total += (bytes + 255) / 256 * 256; return s; };
+  Seg in[] = {seg(frame_start, nullptr, 4 * (np + 1)), seg(imu_range, nullptr, 8 * np), seg(t_frame, nullptr, 8 * nf), seg(q_frame, nullptr, 32 * nf),
+              seg(p_frame, nullptr, 24 * nf), seg(t, nullptr, 8 * (size_t)ns), seg(w, nullptr, 24 * (size_t)ns), seg(a, nullptr, 24 * (size_t)ns)};
+  const size_t in_bytes = total;
+  Seg out[] = {seg(nullptr, gravity, 24 * np), seg(nullptr, bg, 24 * np), seg(nullptr, scale, 8 * np), seg(nullptr, excitation, 8 * np),
+               seg(nullptr, gyro_rank, 4 * np), seg(nullptr, status, 4 * np), seg(nullptr, velocity, 24 * nf), seg(nullptr, q_out, 32 * nf),
+               seg(nullptr, p_out, 24 * nf), seg(nullptr, v_out, 24 * nf)};
+  const size_t out_bytes = total - in_bytes;
+  const Seg s_own = seg(nullptr, nullptr, 4 * (nf + np)), s_fs = seg(nullptr, nullptr, 8 * nf * bsg::kAlignFrameScratch),
+            s_ps = seg(nullptr, nullptr, 8 * np * bsg::kAlignPathScratch);
+  std::vector<unsigned char> h(std::max(in_bytes, out_bytes), 0);
+  for (const Seg& s : in) if (s.bytes) std::memcpy(h.data() + s.off, s.src, s.bytes);
+  unsigned char* d = nullptr;
+  if (hipMalloc((void**)&d, total + 256) != hipSuccess) { (void)hipGetLastError(); return BSGPU_ERR_DEVICE; }
+  int rc = BSGPU_OK;
+  if (hipMemcpy(d, h.data(), in_bytes, hipMemcpyHostToDevice) != hipSuccess) rc = BSGPU_ERR_DEVICE;
+  if (rc == BSGPU_OK) {
+    auto D = [&](const Seg& s) { return (double*)(d + s.off); };
+    auto I = [&](const Seg& s) { return (int*)(d + s.off); };
+    bsg::launch_inertial_alignment(nullptr, n_paths, I(in[0]), D(in[2]), D(in[3]), D(in[4]), I(in[1]), D(in[5]), D(in[6]), D(in[7]),
+                                   bridge_gap, min_excitation, apply_scale, scale_min, scale_max, rank_tol, D(out[0]), D(out[1]), D(out[2]),
+                                   D(out[3]), I(out[4]), D(out[6]), D(out[7]), D(out[8]), D(out[9]), I(out[5]), I(s_own), D(s_fs), D(s_ps));
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(h.data(), d + in_bytes, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = BSGPU_ERR_DEVICE;
+  }
+  (void)hipFree(d);
+  if (rc != BSGPU_OK) { (void)hipGetLastError(); return rc; }
+  for (const Seg& s : out) if (s.bytes) std::memcpy(s.dst, h.data() + (s.off - in_bytes), s.bytes);
+  return BSGPU_OK;
 } catch (...) { return api_exception(nullptr); }
 
 int bsgpu_triangulate(bsgpu_ctx* c, int32_t n_tracks, const int32_t* track_start, const int32_t* q_block, const int32_t* p_block,

@@ -540,6 +540,13 @@ void launch_reproj_errors(hipStream_t s, const Visual& v, const SmallGroup& dens
                           double* out_dense);
 void launch_preintegrate(hipStream_t s, int n_int, const int* sample_start, const double* ts, const double* wm, const double* am,
                          const double* t_end, const double* bg, const double* ba, const double* covs, double info_weight, double* out);
+// visual-inertial alignment (k_align.hip, bsgpu_inertial_alignment): one workgroup per path; arguments as the C-ABI's, on the device;
+// own: total frames + n_paths ints, fs: total frames x kAlignFrameScratch, ps: n_paths x kAlignPathScratch (inertial_align.h)
+void launch_inertial_alignment(hipStream_t s, int n_paths, const int* frame_start, const double* t_frame, const double* q_frame,
+                               const double* p_frame, const int* imu_range, const double* t, const double* w, const double* a,
+                               int bridge_gap, double min_excitation, int apply_scale, double scale_min, double scale_max, double rank_tol,
+                               double* gravity, double* bg, double* scale, double* excitation, int* gyro_rank, double* velocity,
+                               double* q_out, double* p_out, double* v_out, int* status, int* own, double* fs, double* ps);
 void launch_triangulate(hipStream_t s, int n_tracks, const int* track_start, const int2* pose_off, const double2* pix, const double* x,
                         const DevCamera& cam, bool truncate, double max_dist, double max_reproj, double* points, int* status);
 // frame localisation (k_loc.hip, bsgpu_localize_frames): one workgroup per frame; pts (3 per observation) or pt_off (offset of the

@@ -240,4 +240,56 @@ BSG_PRE_FN void preintegrate_interval(int s0, int s1, const double* __restrict__
   for (int i = 0; i < 225; ++i) o[62 + i] = info_weight * U[i];
 }
 
+// The same interval without covariance and information — Integrate(te, bg, ba, jacobian, no covariance, no information), what
+// imu::EstimateParameters asks of its frames (inertial_align.h).  Increment's state update and its dq_dbg update with the arithmetic
+// of preintegrate_interval's `increment`; nothing of the 15 x 15 covariance, its two Cholesky factorisations or the other four
+// bias Jacobians.  s_bridge >= 0: one increment of ts[s0] - t_bridge with the sample s_bridge runs first (skipped, like the
+// remainder, when it is not longer than 1e-12), so that the delta starts at t_bridge instead of at its first sample.
+constexpr int kPreintDelta = 20;   // dt, dq[4], dp[3], dv[3], dq_dbg[9]
+BSG_PRE_FN void preintegrate_delta(int s0, int s1, const double* __restrict__ ts, const double* __restrict__ wm,
+                                   const double* __restrict__ am, double te, const double* __restrict__ bg_in,
+                                   const double* __restrict__ ba_in, int s_bridge, double t_bridge, double* __restrict__ o) {
+  const double bg[3] = {bg_in[0], bg_in[1], bg_in[2]}, ba[3] = {ba_in[0], ba_in[1], ba_in[2]};
+  double dt_tot = 0.0, q[4] = {1, 0, 0, 0}, p[3] = {0, 0, 0}, v[3] = {0, 0, 0};
+  M3 dq_dbg = m3_zero();
+
+  auto increment = [&](double dt, const double* wraw, const double* araw) {   // preintegrator.cpp:26-36, :78-88
+    const double w[3] = {wraw[0] - bg[0], wraw[1] - bg[1], wraw[2] - bg[2]}, a[3] = {araw[0] - ba[0], araw[1] - ba[1], araw[2] - ba[2]};
+    const double wdt[3] = {w[0] * dt, w[1] * dt, w[2] * dt}, whalf[3] = {0.5 * wdt[0], 0.5 * wdt[1], 0.5 * wdt[2]};
+    const M3 R_full = so3_exp(wdt), Jr = so3_jr(wdt);
+    const M3 Rt = m3_t(R_full);
+    dq_dbg = m3_axpy(-dt, Jr, m3_mul(Rt, dq_dbg));
+    double qh[4], qm[4], qf[4], qn[4];
+    quat_from_aa_unit(whalf, qh);
+    pre_quat_mul(q, qh, qm);
+    const M3 Rm = pre_quat_to_rot(qm);
+    const double amid[3] = {Rm.m[0] * a[0] + Rm.m[1] * a[1] + Rm.m[2] * a[2], Rm.m[3] * a[0] + Rm.m[4] * a[1] + Rm.m[5] * a[2],
+                            Rm.m[6] * a[0] + Rm.m[7] * a[1] + Rm.m[8] * a[2]};
+    dt_tot += dt;
+    for (int i = 0; i < 3; ++i) p[i] += dt * v[i] + 0.5 * dt * dt * amid[i];
+    for (int i = 0; i < 3; ++i) v[i] += dt * amid[i];
+    quat_from_aa_unit(wdt, qf);
+    pre_quat_mul(q, qf, qn);
+    const double nn = sqrt(qn[0] * qn[0] + qn[1] * qn[1] + qn[2] * qn[2] + qn[3] * qn[3]);
+    for (int i = 0; i < 4; ++i) q[i] = qn[i] / nn;
+  };
+
+  if (s_bridge >= 0 && s1 > s0) {
+    const double dt = ts[s0] - t_bridge;
+    if (dt > 1e-12) increment(dt, wm + 3 * s_bridge, am + 3 * s_bridge);
+  }
+  for (int s = s0; s + 1 < s1; ++s) {                       // :96-102
+    if (ts[s + 1] > te + 1e-12) break;
+    increment(ts[s + 1] - ts[s], wm + 3 * s, am + 3 * s);
+  }
+  if (s1 > s0) {                                            // :104-108 remainder with the last sample
+    const double dt = te - ts[s1 - 1];
+    if (dt > 1e-12) increment(dt, wm + 3 * (s1 - 1), am + 3 * (s1 - 1));
+  }
+  o[0] = dt_tot;
+  for (int i = 0; i < 4; ++i) o[1 + i] = q[i];
+  for (int i = 0; i < 3; ++i) { o[5 + i] = p[i]; o[8 + i] = v[i]; }
+  for (int i = 0; i < 9; ++i) o[11 + i] = dq_dbg.m[i];
+}
+
 }  // namespace bsg

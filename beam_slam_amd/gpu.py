@@ -70,6 +70,40 @@ def preintegrate(sample_start, t, w, a, t_end, bg, ba, cov_w, cov_a, cov_bg, cov
     return out
 
 
+def inertial_alignment(frame_start, t_frame, q_frame, p_frame, imu_range, t, w, a, bridge_gap=False,
+                       min_excitation=capi.ALIGN_MIN_EXCITATION, apply_scale=True, scale_min=capi.ALIGN_SCALE_MIN,
+                       scale_max=capi.ALIGN_SCALE_MAX, rank_tol=capi.ALIGN_RANK_TOL, device=0):
+    """bsgpu_inertial_alignment: imu::EstimateParameters, the scale gate and AlignPathAndVelocities for a batch of candidate paths.
+    Path k holds frames [frame_start[k], frame_start[k+1]) (stamp, T_WORLD_BASELINK as wxyz / xyz) and the IMU samples
+    [imu_range[k, 0], imu_range[k, 1]) of t / w / a.  Returns a dict of arrays: gravity (P x 3), bg (P x 3), scale, excitation,
+    gyro_rank, status (P); velocity, p_out, v_out (F x 3), q_out (F x 4)."""
+    import numpy as np
+    f64 = lambda x, shape: np.ascontiguousarray(x, np.float64).reshape(shape)
+    fs = np.ascontiguousarray(frame_start, np.int32).reshape(-1)
+    P = fs.size - 1
+    ir = np.ascontiguousarray(imu_range, np.int32).reshape(-1, 2)
+    tf, qf, pf = f64(t_frame, (-1,)), f64(q_frame, (-1, 4)), f64(p_frame, (-1, 3))
+    t, w, a = f64(t, (-1,)), f64(w, (-1, 3)), f64(a, (-1, 3))
+    F = tf.size
+    if P < 0 or ir.shape[0] != P or qf.shape[0] != F or pf.shape[0] != F or w.shape[0] != t.size or a.shape[0] != t.size:
+        raise capi.SolverError(capi.ERR_INVALID, "inertial_alignment: array sizes do not agree")
+    if P > 0 and (int(fs.max()) > F or int(ir.max()) > t.size):
+        raise capi.SolverError(capi.ERR_INVALID, "inertial_alignment: frame_start / imu_range name more frames or samples than were passed")
+    out = dict(gravity=np.zeros((P, 3)), bg=np.zeros((P, 3)), scale=np.zeros(P), excitation=np.zeros(P), gyro_rank=np.zeros(P, np.int32),
+               velocity=np.zeros((F, 3)), q_out=np.zeros((F, 4)), p_out=np.zeros((F, 3)), v_out=np.zeros((F, 3)), status=np.zeros(P, np.int32))
+    fn = lib().bsgpu_inertial_alignment
+    fn.argtypes = capi.INERTIAL_ALIGNMENT_ARGTYPES
+    _dp, _ip = capi._dp, capi._ip
+    d = lambda x: x.ctypes.data_as(_dp)
+    rc = fn(device, P, fs.ctypes.data_as(_ip), d(tf), d(qf), d(pf), ir.ctypes.data_as(_ip), d(t), d(w), d(a), int(bool(bridge_gap)),
+            float(min_excitation), int(bool(apply_scale)), float(scale_min), float(scale_max), float(rank_tol), d(out["gravity"]),
+            d(out["bg"]), d(out["scale"]), d(out["excitation"]), out["gyro_rank"].ctypes.data_as(_ip), d(out["velocity"]), d(out["q_out"]),
+            d(out["p_out"]), d(out["v_out"]), out["status"].ctypes.data_as(_ip))
+    if rc != 0:
+        raise capi.SolverError(rc, "bsgpu_inertial_alignment failed")
+    return out
+
+
 class GpuSolver(capi.Solver):
     """One bsgpu context on HIP device `device`."""
 

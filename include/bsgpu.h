@@ -482,6 +482,57 @@ int bsgpu_preintegrate(int device, int32_t n_intervals, const int32_t* sample_st
                        const double* cov_a, const double* cov_bg, const double* cov_ba, double info_weight,
                        double* consts_out);
 
+/* Visual-inertial alignment for a batch of candidate paths — what SLAMInitialization does between the up-to-scale camera path and
+ * its first large solve: imu::EstimateParameters (bs_models/src/lib/imu/inertial_alignment.cpp:4-202: gyroscope bias, gravity,
+ * metric scale, a velocity per frame), the scale gate (bs_models/src/slam_initialization.cpp:312-316) and AlignPathAndVelocities
+ * (:400-431).  Path k holds frames [frame_start[k], frame_start[k+1]) (frame_start[0] == 0, non-decreasing; stamps strictly
+ * increasing within a path; T_WORLD_BASELINK as q_frame wxyz / p_frame xyz) and the IMU samples [imu_range[2k], imu_range[2k+1]) of
+ * t / w / a (as in bsgpu_preintegrate; the arrays hold max(imu_range[2k+1]) samples).  The ranges of different paths may overlap or
+ * coincide.  A path's results never depend on the other paths of the call, bit for bit.  n_paths == 0 does nothing.  Argument
+ * errors -> INVALID: frame_start[0] != 0 or decreasing, a range with first < 0 or last < first, NULL where an array is needed.
+ * Per path, in this order (status: BSGPU_ALIGN_*; TOO_FEW_FRAMES is decided before the samples are looked at):
+ * (a) Frames.  Frame f owns the samples of the range with t < t_frame[f] that no earlier frame owns (frame 0: every sample before
+ *     the first pose).  BAD_IMU where the reference throws or asserts (:23-30, :50-55, preintegrator.cpp:30): a frame owns no
+ *     sample, the range's second sample is later than t_frame[0] (or there is none), sample times not strictly increasing, a delta
+ *     of no duration, any non-finite input of the path.  Fewer than 4 frames: TOO_FEW_FRAMES (6 (N - 1) rows for 4 + 3 N unknowns;
+ *     ComputePathWithVision asserts more than 3 images).
+ * (b) Deltas.  Integrate(t_frame[f], bg, 0, jacobian, no covariance, no information) (preintegrator.cpp:91-115) over the owned
+ *     samples: consecutive samples, then the remainder from the last one to the stamp — so the delta of frame f starts at its first
+ *     owned sample, up to one IMU period after t_frame[f-1].  bridge_gap == 0 is this, the reference.  bridge_gap != 0 runs one
+ *     increment first for f >= 1, from t_frame[f-1] to the first owned sample with the last sample frame f-1 owns (skipped when not
+ *     longer than 1e-12 s): the delta then spans exactly [t_frame[f-1], t_frame[f]].
+ * (c) Excitation (:114-136), deltas at zero bias: g_f = dv_f / dt_f for all N frames, mean = (sum g_f) / (N - 1) as the reference
+ *     divides, excitation = sqrt(sum |g_f - mean|^2 / (N - 1)).  The sum starts from zero; the reference's starts from an
+ *     uninitialised Eigen::Vector3d.  excitation < min_excitation (reference: 0.25): NOT_EXCITED.
+ * (d) Gyroscope bias (:138-161), over j >= 1: A = sum J^T J, b = sum J^T Log(normalize((q_{j-1} dq_j)^* q_j)), J = dq_dbg_j;
+ *     bg = A^+ b through a Jacobi eigen-decomposition of the symmetric 3 x 3, an eigenvalue <= 3 * 2^-52 * lambda_max counting as zero
+ *     (Eigen::JacobiSVD's default threshold — recalled, not verified); gyro_rank: the eigenvalues kept.  Log: the rotation vector,
+ *     angle in [0, pi] ([EXT] beam::RToLieAlgebra — recalled, not verified), taken from the quaternion.
+ * (e) Gravity, scale, velocities (:163-202), deltas re-integrated at (bg, 0): for i = j - 1 and dt, dp, dv of frame j
+ *         -1/2 dt^2 g + (p_j - p_i) s - dt v_i = R(q_i) dp_j,      -dt g - v_i + v_j = R(q_i) dv_j
+ *     in the least-squares sense by Householder reflections on the unknowns ordered v_0 .. v_{N-1}, g, s (not the normal
+ *     equations).  RANK_DEFICIENT when the smallest |diagonal| of that triangular factor is <= rank_tol (1e-10) x the largest — a
+ *     path whose positions are all equal has a zero scale column; the reference's fullPivHouseholderQr returns a basic solution
+ *     there — or when the gravity estimate has no direction.  Otherwise gravity = normalize(g) * 9.80665, scale = s,
+ *     velocity[f] = v_f.
+ * (f) Gate and alignment.  apply_scale != 0 and scale outside [scale_min, scale_max] (reference: 0.02, 1.0): SCALE_REJECTED.
+ *     Otherwise q_a = FromTwoVectors(gravity, (0, 0, -9.80665)), q_out = q_a q, p_out = q_a p (times scale when apply_scale),
+ *     v_out = q_a velocity (never scaled, as in the reference).  FromTwoVectors is Eigen's formula where 1 + cos > 2^-52; for
+ *     antiparallel vectors the half turn about the unit vector gravity x e_k, e_k the coordinate axis of gravity's smallest
+ *     |component| — not Eigen's SVD branch.
+ * Outputs per path: gravity (3), bg (3), scale, excitation, gyro_rank; per frame: velocity (3: the least-squares velocities in the
+ * input world), q_out, p_out, v_out.  ba is no output: the reference never estimates it (:14).  What a status leaves: TOO_FEW_FRAMES
+ * and BAD_IMU: gravity = bg = 0, scale = 1, excitation = 0, gyro_rank = 0, velocity = v_out = 0, q_out / p_out the inputs.
+ * NOT_EXCITED: the same with excitation.  RANK_DEFICIENT: excitation, bg and gyro_rank as estimated, the rest as before.
+ * SCALE_REJECTED: every estimate, q_out / p_out the inputs and v_out = velocity.                                                  */
+enum { BSGPU_ALIGN_OK = 0, BSGPU_ALIGN_TOO_FEW_FRAMES = 1, BSGPU_ALIGN_BAD_IMU = 2, BSGPU_ALIGN_NOT_EXCITED = 3,
+       BSGPU_ALIGN_RANK_DEFICIENT = 4, BSGPU_ALIGN_SCALE_REJECTED = 5 };
+int bsgpu_inertial_alignment(int device, int32_t n_paths, const int32_t* frame_start, const double* t_frame, const double* q_frame,
+                             const double* p_frame, const int32_t* imu_range, const double* t, const double* w, const double* a,
+                             int32_t bridge_gap, double min_excitation, int32_t apply_scale, double scale_min, double scale_max,
+                             double rank_tol, double* gravity, double* bg, double* scale, double* excitation, int32_t* gyro_rank,
+                             double* velocity, double* q_out, double* p_out, double* v_out, int32_t* status);
+
 /* Landmark triangulation for a batch of feature tracks at the context's CURRENT values (after a solve: the values the
  * solve left on the device) — VisualOdometry::TriangulateLandmark (bs_models/src/visual_odometry.cpp:532-610) and
  * SLAMInitialization::TriangulateLandmark (bs_models/src/slam_initialization.cpp:699-701), i.e. the [EXT]
