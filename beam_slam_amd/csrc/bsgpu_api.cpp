@@ -4,13 +4,13 @@
 // (bs_optimizers/src/fixed_lag_smoother.cpp:281): [EXT] fuse HashGraph::createProblem (finalize(), bsgpu_finalize.cpp:
 // flattening to device tables) and [EXT] ceres::Solve with TRUST_REGION / LEVENBERG_MARQUARDT /
 // SPARSE_NORMAL_CHOLESKY (solve(), bsgpu_solve.cpp: a restatement of Ceres' TrustRegionMinimizer +
-// LevenbergMarquardtStrategy driving device kernels).  This file: the entry points themselves.
+// LevenbergMarquardtStrategy driving device kernels).  This file: the entry points of the context, its factors, solves, marginals
+// and covariances, and the profiling hooks; the front-end entry points (pre-integration ... RANSAC) are bsgpu_frontend.cpp's.
 // There is no CPU fallback: without a HIP device bsgpu_create() fails.
 #include <thread>
 
 #include "bsgpu_ctx.h"
 #include "bsgpu_env.h"
-#include "inertial_align.h"
 
 using namespace bsg;
 
@@ -987,463 +987,6 @@ int bsgpu_reprojection_errors(bsgpu_ctx* c, double* err) try {
   auto slot = [&](int src) { const int t = src >> 28, f = src & ((1 << 28) - 1); return (t == BSGPU_F_REPROJ ? 0 : n0) + f; };
   for (int i = 0; i < V.n; ++i) err[slot(c->vis_src[i])] = h[i];
   for (int i = 0; i < D.n; ++i) err[slot(c->dense_src[i])] = h[(size_t)V.n + i];
-  return BSGPU_OK;
-} catch (...) { return api_exception(c); }
-
-int bsgpu_preintegrate(int device, int32_t n, const int32_t* sample_start, const double* t, const double* w, const double* a,
-                       const double* t_end, const double* bg, const double* ba, const double* cov_w, const double* cov_a,
-                       const double* cov_bg, const double* cov_ba, double info_weight, double* consts_out) try {
-  if (n < 0) return BSGPU_ERR_INVALID;
-  if (n == 0) return BSGPU_OK;
-  if (!sample_start || !t_end || !bg || !ba || !cov_w || !cov_a || !cov_bg || !cov_ba || !consts_out) return BSGPU_ERR_INVALID;
-  // an interval may hold no samples (it stays the identity); the kernel indexes the samples by this table, so it is checked here
-  if (sample_start[0] < 0) return BSGPU_ERR_INVALID;
-  for (int i = 0; i < n; ++i) if (sample_start[i + 1] < sample_start[i]) return BSGPU_ERR_INVALID;
-  const int ns = sample_start[n];
-  if (ns > 0 && (!t || !w || !a)) return BSGPU_ERR_INVALID;
-  if (hipSetDevice(device) != hipSuccess) return BSGPU_ERR_DEVICE;
-  std::vector<double> covs(36);
-  std::memcpy(&covs[0], cov_w, 72); std::memcpy(&covs[9], cov_a, 72); std::memcpy(&covs[18], cov_bg, 72); std::memcpy(&covs[27], cov_ba, 72);
-  std::vector<void*> bufs;
-  auto up = [&](const void* src, size_t bytes) -> void* {
-    void* d = nullptr;
-    if (hipMalloc(&d, bytes) != hipSuccess) return nullptr;
-    bufs.push_back(d);
-    if (src && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
-    return d;
-  };
-  int* d_ss = (int*)up(sample_start, sizeof(int) * (n + 1));
-  double* d_t = (double*)up(ns ? t : nullptr, sizeof(double) * (ns ? ns : 1));
-  double* d_w = (double*)up(ns ? w : nullptr, sizeof(double) * 3 * (ns ? ns : 1));
-  double* d_a = (double*)up(ns ? a : nullptr, sizeof(double) * 3 * (ns ? ns : 1));
-  double* d_te = (double*)up(t_end, sizeof(double) * n);
-  double* d_bg = (double*)up(bg, sizeof(double) * 3 * n);
-  double* d_ba = (double*)up(ba, sizeof(double) * 3 * n);
-  double* d_cov = (double*)up(covs.data(), sizeof(double) * 36);
-  double* d_out = (double*)up(nullptr, sizeof(double) * 287 * (size_t)n);
-  int rc = BSGPU_OK;
-  if (!d_ss || !d_t || !d_w || !d_a || !d_te || !d_bg || !d_ba || !d_cov || !d_out) rc = BSGPU_ERR_DEVICE;
-  if (rc == BSGPU_OK) {
-    launch_preintegrate(nullptr, n, d_ss, d_t, d_w, d_a, d_te, d_bg, d_ba, d_cov, info_weight, d_out);
-    if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess ||
-        hipMemcpy(consts_out, d_out, sizeof(double) * 287 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) rc = BSGPU_ERR_DEVICE;
-  }
-  for (void* p : bufs) (void)hipFree(p);
-  return rc;
-} catch (...) { return api_exception(nullptr); }
-
-int bsgpu_inertial_alignment(int device, int32_t n_paths, const int32_t* frame_start, const double* t_frame, const double* q_frame,
-                             const double* p_frame, const int32_t* imu_range, const double* t, const double* w, const double* a,
-                             int32_t bridge_gap, double min_excitation, int32_t apply_scale, double scale_min, double scale_max,
-                             double rank_tol, double* gravity, double* bg, double* scale, double* excitation, int32_t* gyro_rank,
-                             double* velocity, double* q_out, double* p_out, double* v_out, int32_t* status) try {
-  if (n_paths < 0) return BSGPU_ERR_INVALID;
-  if (n_paths == 0) return BSGPU_OK;
-  if (!frame_start || !imu_range || !gravity || !bg || !scale || !excitation || !gyro_rank || !status) return BSGPU_ERR_INVALID;
-  if (frame_start[0] != 0) return BSGPU_ERR_INVALID;
-  int ns = 0;
-  for (int k = 0; k < n_paths; ++k) {
-    if (frame_start[k + 1] < frame_start[k]) return BSGPU_ERR_INVALID;
-    if (imu_range[2 * k] < 0 || imu_range[2 * k + 1] < imu_range[2 * k]) return BSGPU_ERR_INVALID;
-    ns = std::max(ns, (int)imu_range[2 * k + 1]);
-  }
-  const size_t nf = (size_t)frame_start[n_paths], np = (size_t)n_paths;
-  if (nf > 0 && (!t_frame || !q_frame || !p_frame || !velocity || !q_out || !p_out || !v_out)) return BSGPU_ERR_INVALID;
-  if (ns > 0 && (!t || !w || !a)) return BSGPU_ERR_INVALID;
-  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return BSGPU_ERR_DEVICE; }
-  // one allocation: [inputs | outputs | scratch], every segment on a 256-byte boundary; one copy in, one copy out
-  struct Seg { const void* src; void* dst; size_t bytes, off; };
-  size_t total = 0;
-  auto seg = [&](const void* src, void* dst, size_t bytes) { Seg s{src, dst, bytes, total}; total += (bytes + 255) / 256 * 256; return s; };
-  Seg in[] = {seg(frame_start, nullptr, 4 * (np + 1)), seg(imu_range, nullptr, 8 * np), seg(t_frame, nullptr, 8 * nf), seg(q_frame, nullptr, 32 * nf),
-              seg(p_frame, nullptr, 24 * nf), seg(t, nullptr, 8 * (size_t)ns), seg(w, nullptr, 24 * (size_t)ns), seg(a, nullptr, 24 * (size_t)ns)};
-  const size_t in_bytes = total;
-  Seg out[] = {seg(nullptr, gravity, 24 * np), seg(nullptr, bg, 24 * np), seg(nullptr, scale, 8 * np), seg(nullptr, excitation, 8 * np),
-               seg(nullptr, gyro_rank, 4 * np), seg(nullptr, status, 4 * np), seg(nullptr, velocity, 24 * nf), seg(nullptr, q_out, 32 * nf),
-               seg(nullptr, p_out, 24 * nf), seg(nullptr, v_out, 24 * nf)};
-  const size_t out_bytes = total - in_bytes;
-  const Seg s_own = seg(nullptr, nullptr, 4 * (nf + np)), s_fs = seg(nullptr, nullptr, 8 * nf * bsg::kAlignFrameScratch),
-            s_ps = seg(nullptr, nullptr, 8 * np * bsg::kAlignPathScratch);
-  std::vector<unsigned char> h(std::max(in_bytes, out_bytes), 0);
-  for (const Seg& s : in) if (s.bytes) std::memcpy(h.data() + s.off, s.src, s.bytes);
-  unsigned char* d = nullptr;
-  if (hipMalloc((void**)&d, total + 256) != hipSuccess) { (void)hipGetLastError(); return BSGPU_ERR_DEVICE; }
-  int rc = BSGPU_OK;
-  if (hipMemcpy(d, h.data(), in_bytes, hipMemcpyHostToDevice) != hipSuccess) rc = BSGPU_ERR_DEVICE;
-  if (rc == BSGPU_OK) {
-    auto D = [&](const Seg& s) { return (double*)(d + s.off); };
-    auto I = [&](const Seg& s) { return (int*)(d + s.off); };
-    bsg::launch_inertial_alignment(nullptr, n_paths, I(in[0]), D(in[2]), D(in[3]), D(in[4]), I(in[1]), D(in[5]), D(in[6]), D(in[7]),
-                                   bridge_gap, min_excitation, apply_scale, scale_min, scale_max, rank_tol, D(out[0]), D(out[1]), D(out[2]),
-                                   D(out[3]), I(out[4]), D(out[6]), D(out[7]), D(out[8]), D(out[9]), I(out[5]), I(s_own), D(s_fs), D(s_ps));
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
-        hipMemcpy(h.data(), d + in_bytes, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = BSGPU_ERR_DEVICE;
-  }
-  (void)hipFree(d);
-  if (rc != BSGPU_OK) { (void)hipGetLastError(); return rc; }
-  for (const Seg& s : out) if (s.bytes) std::memcpy(s.dst, h.data() + (s.off - in_bytes), s.bytes);
-  return BSGPU_OK;
-} catch (...) { return api_exception(nullptr); }
-
-int bsgpu_triangulate(bsgpu_ctx* c, int32_t n_tracks, const int32_t* track_start, const int32_t* q_block, const int32_t* p_block,
-                      const double* pixels, int32_t camera, int32_t truncate_pixels, double max_dist, double max_reproj, double* points,
-                      int32_t* status) try {
-  if (!c) return BSGPU_ERR_INVALID;
-  if (n_tracks < 0 || !track_start || !points || !status) return fail(c, BSGPU_ERR_INVALID, "null argument");
-  if (n_tracks == 0) return BSGPU_OK;
-  const int n_obs = track_start[n_tracks];
-  if (track_start[0] != 0 || n_obs < 0 || (n_obs > 0 && (!q_block || !p_block || !pixels)))
-    return fail(c, BSGPU_ERR_INVALID, "triangulate: malformed track table");
-  if (camera < 0 || camera >= (int)c->cams.size()) return fail(c, BSGPU_ERR_INVALID, "camera index out of range");
-  std::vector<int32_t> pose_off((size_t)2 * n_obs);
-  for (int i = 0; i < n_tracks; ++i)
-    if (track_start[i + 1] < track_start[i]) return fail(c, BSGPU_ERR_INVALID, "triangulate: track_start must be non-decreasing");
-  for (int o = 0; o < n_obs; ++o) {
-    const int qb = q_block[o], pb = p_block[o];
-    if (qb < 0 || qb >= c->nb || pb < 0 || pb >= c->nb) return fail(c, BSGPU_ERR_INVALID, "triangulate: block out of range");
-    if (c->size[qb] != 4 || c->size[pb] != 3) return fail(c, BSGPU_ERR_INVALID, "triangulate: view blocks must be (orientation[4], position[3])");
-    pose_off[2 * (size_t)o] = c->off[qb];
-    pose_off[2 * (size_t)o + 1] = c->off[pb];
-  }
-  int rc = finalize(c);
-  if (rc != BSGPU_OK) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  const bsgpu_camera& hc = c->cams[camera];
-  DevCamera cam;
-  cam.fx = hc.fx; cam.fy = hc.fy; cam.cx = hc.cx; cam.cy = hc.cy;
-  std::memcpy(cam.R, hc.R_cam_baselink, sizeof(cam.R));
-  std::memcpy(cam.t, hc.t_cam_baselink, sizeof(cam.t));
-  int *d_start = nullptr, *d_status = nullptr;
-  int2* d_off = nullptr;
-  double2* d_pix = nullptr;
-  double* d_pts = nullptr;
-  auto release = [&]() { (void)hipFree(d_start); (void)hipFree(d_status); (void)hipFree(d_off); (void)hipFree(d_pix); (void)hipFree(d_pts); };
-  hipError_t e = hipMalloc((void**)&d_start, sizeof(int) * ((size_t)n_tracks + 1));
-  if (e == hipSuccess) e = hipMalloc((void**)&d_status, sizeof(int) * (size_t)n_tracks);
-  if (e == hipSuccess) e = hipMalloc((void**)&d_pts, sizeof(double) * 3 * (size_t)n_tracks);
-  if (e == hipSuccess && n_obs) e = hipMalloc((void**)&d_off, sizeof(int2) * (size_t)n_obs);
-  if (e == hipSuccess && n_obs) e = hipMalloc((void**)&d_pix, sizeof(double2) * (size_t)n_obs);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_start, track_start, sizeof(int) * ((size_t)n_tracks + 1), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && n_obs) e = hipMemcpyAsync(d_off, pose_off.data(), sizeof(int2) * (size_t)n_obs, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && n_obs) e = hipMemcpyAsync(d_pix, pixels, sizeof(double2) * (size_t)n_obs, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    launch_triangulate(c->stream, n_tracks, d_start, d_off, d_pix, c->d_x, cam, truncate_pixels != 0, max_dist, max_reproj, d_pts, d_status);
-    e = hipMemcpyAsync(points, d_pts, sizeof(double) * 3 * (size_t)n_tracks, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(status, d_status, sizeof(int) * (size_t)n_tracks, hipMemcpyDeviceToHost, c->stream);
-  const hipError_t e2 = hipStreamSynchronize(c->stream);
-  release();
-  if (e != hipSuccess || e2 != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "triangulate: device error");
-  return BSGPU_OK;
-} catch (...) { return api_exception(c); }
-
-int bsgpu_localize_frames(bsgpu_ctx* c, int32_t n_frames, const int32_t* obs_start, const double* pixels, const double* points,
-                          const int32_t* lm_block, const int32_t* camera, const double* q_init, const double* p_init,
-                          int32_t loss_kind, double loss_a, double sqrt_info, int32_t truncate_pixels, int32_t min_points,
-                          int32_t image_width, int32_t image_height, const bsgpu_options* options, double* q_out, double* p_out,
-                          double* cov_out, double* avg_reproj, double* final_cost, int32_t* iterations, int32_t* status) try {
-  if (!c) return BSGPU_ERR_INVALID;
-  if (n_frames < 0 || !obs_start || !camera || !q_init || !p_init || !options || !q_out || !p_out || !status)
-    return fail(c, BSGPU_ERR_INVALID, "localize_frames: null argument");
-  if ((points == nullptr) == (lm_block == nullptr)) return fail(c, BSGPU_ERR_INVALID, "localize_frames: pass exactly one of points and lm_block");
-  if (options->trust_region_strategy_type != BSGPU_TR_LEVENBERG_MARQUARDT)
-    return fail(c, BSGPU_ERR_UNSUPPORTED, "localize_frames: its in-kernel loop is Levenberg-Marquardt only (trust_region_strategy_type must be 0)");
-  if (loss_kind < BSGPU_LOSS_TRIVIAL || loss_kind > BSGPU_LOSS_HUBER) return fail(c, BSGPU_ERR_INVALID, "unknown loss kind");
-  if (obs_start[0] != 0) return fail(c, BSGPU_ERR_INVALID, "localize_frames: obs_start[0] must be 0");
-  for (int f = 0; f < n_frames; ++f) {
-    if (obs_start[f + 1] < obs_start[f]) return fail(c, BSGPU_ERR_INVALID, "localize_frames: obs_start must be non-decreasing");
-    if (camera[f] < 0 || camera[f] >= (int)c->cams.size()) return fail(c, BSGPU_ERR_INVALID, "camera index out of range");
-  }
-  const int n_obs = obs_start[n_frames];
-  if (n_obs > 0 && !pixels) return fail(c, BSGPU_ERR_INVALID, "localize_frames: null pixels");
-  std::vector<int32_t> pt_off;
-  if (lm_block) {
-    if (!c->finalized || !c->d_x) return fail(c, BSGPU_ERR_INVALID, "localize_frames: lm_block needs the context's values on the device (finalize or solve first)");
-    pt_off.resize((size_t)n_obs);
-    for (int o = 0; o < n_obs; ++o) {
-      const int b = lm_block[o];
-      if (b < 0 || b >= c->nb) return fail(c, BSGPU_ERR_INVALID, "localize_frames: block out of range");
-      if (c->size[b] != 3 || c->manifold[b] != BSGPU_MANIFOLD_EUCLIDEAN) return fail(c, BSGPU_ERR_INVALID, "localize_frames: lm_block must name 3-d Euclidean blocks");
-      pt_off[o] = c->off[b];
-    }
-  }
-  if (n_frames == 0) return BSGPU_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // one device buffer: inputs [obs_start | camera | pt_off | cameras | pixels | points | poses], outputs [per-frame doubles | ints]
-  std::vector<DevCamera> cams(c->cams.size());
-  for (size_t i = 0; i < cams.size(); ++i) {
-    const bsgpu_camera& hc = c->cams[i];
-    cams[i].fx = hc.fx; cams[i].fy = hc.fy; cams[i].cx = hc.cx; cams[i].cy = hc.cy;
-    std::memcpy(cams[i].R, hc.R_cam_baselink, sizeof(cams[i].R));
-    std::memcpy(cams[i].t, hc.t_cam_baselink, sizeof(cams[i].t));
-  }
-  std::vector<double> pose((size_t)7 * n_frames);
-  for (int f = 0; f < n_frames; ++f) {
-    std::memcpy(&pose[7 * (size_t)f], q_init + 4 * (size_t)f, 4 * sizeof(double));
-    std::memcpy(&pose[7 * (size_t)f + 4], p_init + 3 * (size_t)f, 3 * sizeof(double));
-  }
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_start = al(sizeof(int32_t) * ((size_t)n_frames + 1)), b_cam = al(sizeof(int32_t) * (size_t)n_frames),
-               b_off = al(sizeof(int32_t) * pt_off.size()), b_cams = al(sizeof(DevCamera) * cams.size()),
-               b_pix = al(sizeof(double) * 2 * (size_t)n_obs), b_pts = points ? al(sizeof(double) * 3 * (size_t)n_obs) : 0,
-               b_pose = al(sizeof(double) * pose.size());
-  const size_t in_bytes = b_start + b_cam + b_off + b_cams + b_pix + b_pts + b_pose;
-  const size_t out_d = sizeof(double) * kLocOutStride * (size_t)n_frames, out_i = sizeof(int32_t) * 2 * (size_t)n_frames;
-  std::vector<char> h_in(in_bytes);
-  std::vector<char> h_out(out_d + out_i);
-  size_t at = 0;
-  auto put = [&](const void* src, size_t bytes, size_t span) { if (bytes) std::memcpy(h_in.data() + at, src, bytes); const size_t o = at; at += span; return o; };
-  const size_t o_start = put(obs_start, sizeof(int32_t) * ((size_t)n_frames + 1), b_start);
-  const size_t o_cam = put(camera, sizeof(int32_t) * (size_t)n_frames, b_cam);
-  const size_t o_off = put(pt_off.data(), sizeof(int32_t) * pt_off.size(), b_off);
-  const size_t o_cams = put(cams.data(), sizeof(DevCamera) * cams.size(), b_cams);
-  const size_t o_pix = put(pixels, sizeof(double) * 2 * (size_t)n_obs, b_pix);
-  const size_t o_pts = put(points, points ? sizeof(double) * 3 * (size_t)n_obs : 0, b_pts);
-  const size_t o_pose = put(pose.data(), sizeof(double) * pose.size(), b_pose);
-  char* d = nullptr;
-  if (hipMalloc((void**)&d, in_bytes + out_d + out_i) != hipSuccess) { (void)hipGetLastError(); return fail(c, BSGPU_ERR_DEVICE, "localize_frames: out of device memory"); }
-  hipError_t e = hipMemcpyAsync(d, h_in.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    launch_localize(c->stream, n_frames, (const int*)(d + o_start), (const double2*)(d + o_pix), points ? (const double*)(d + o_pts) : nullptr,
-                    lm_block ? (const int*)(d + o_off) : nullptr, lm_block ? c->d_x : nullptr, (const DevCamera*)(d + o_cams),
-                    (const int*)(d + o_cam), (const double*)(d + o_pose), loss_kind, loss_a, sqrt_info, truncate_pixels != 0 ? 1 : 0,
-                    min_points, image_width, image_height, *options, (double*)(d + in_bytes), (int*)(d + in_bytes + out_d));
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d + in_bytes, out_d + out_i, hipMemcpyDeviceToHost, c->stream);
-  const hipError_t e2 = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "localize_frames: device error");
-  const double* od = (const double*)h_out.data();
-  const int32_t* oi = (const int32_t*)(h_out.data() + out_d);
-  for (int f = 0; f < n_frames; ++f) {
-    const double* r = od + (size_t)kLocOutStride * f;
-    std::memcpy(q_out + 4 * (size_t)f, r, 4 * sizeof(double));
-    std::memcpy(p_out + 3 * (size_t)f, r + 4, 3 * sizeof(double));
-    if (final_cost) final_cost[f] = r[7];
-    if (avg_reproj) avg_reproj[f] = r[8];
-    if (cov_out) std::memcpy(cov_out + 36 * (size_t)f, r + 9, 36 * sizeof(double));
-    if (iterations) iterations[f] = oi[2 * f];
-    status[f] = oi[2 * f + 1];
-  }
-  return BSGPU_OK;
-} catch (...) { return api_exception(c); }
-
-int bsgpu_essential_ransac(bsgpu_ctx* c, int32_t n_sets, const int32_t* match_start, const double* px_prev, const double* px_cur,
-                           const double* K, double prob, double threshold_px, int32_t max_iters, uint64_t seed, uint8_t* mask, double* E,
-                           int32_t* n_inliers, int32_t* n_iters, int32_t* best_sample, int32_t* status) try {
-  if (!c) return BSGPU_ERR_INVALID;
-  if (n_sets < 0 || !match_start || !px_prev || !px_cur || !K || !mask || !status)
-    return fail(c, BSGPU_ERR_INVALID, "essential_ransac: null argument");
-  if (!(prob > 0.0 && prob < 1.0)) return fail(c, BSGPU_ERR_INVALID, "essential_ransac: prob must lie inside (0, 1)");
-  if (!(threshold_px > 0.0) || max_iters <= 0) return fail(c, BSGPU_ERR_INVALID, "essential_ransac: threshold_px and max_iters must be positive");
-  if (match_start[0] != 0) return fail(c, BSGPU_ERR_INVALID, "essential_ransac: match_start[0] must be 0");
-  for (int k = 0; k < n_sets; ++k) {
-    if (match_start[k + 1] < match_start[k]) return fail(c, BSGPU_ERR_INVALID, "essential_ransac: match_start must be non-decreasing");
-    if (!(K[4 * (size_t)k] > 0.0) || !(K[4 * (size_t)k + 1] > 0.0)) return fail(c, BSGPU_ERR_INVALID, "essential_ransac: focal lengths must be positive");
-  }
-  for (int k = 0; k < n_sets; ++k)
-    if (match_start[k + 1] - match_start[k] > BSGPU_RANSAC_MAX_MATCHES)
-      return fail(c, BSGPU_ERR_UNSUPPORTED, "essential_ransac: a set holds more than BSGPU_RANSAC_MAX_MATCHES matches");
-  if (n_sets == 0) return BSGPU_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // one device buffer: inputs [match_start | K | px_prev | px_cur], outputs [E | per-set ints | mask]
-  const size_t n_m = (size_t)match_start[n_sets];
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_start = al(sizeof(int32_t) * ((size_t)n_sets + 1)), b_K = al(sizeof(double) * 4 * (size_t)n_sets), b_px = al(sizeof(double) * 2 * n_m);
-  const size_t in_bytes = b_start + b_K + 2 * b_px;
-  const size_t out_E = al(sizeof(double) * 9 * (size_t)n_sets), out_i = al(sizeof(int32_t) * kRansacOutInts * (size_t)n_sets), out_m = al(n_m);
-  std::vector<char> h_in(in_bytes), h_out(out_E + out_i + out_m);
-  std::memcpy(h_in.data(), match_start, sizeof(int32_t) * ((size_t)n_sets + 1));
-  std::memcpy(h_in.data() + b_start, K, sizeof(double) * 4 * (size_t)n_sets);
-  if (n_m) {
-    std::memcpy(h_in.data() + b_start + b_K, px_prev, sizeof(double) * 2 * n_m);
-    std::memcpy(h_in.data() + b_start + b_K + b_px, px_cur, sizeof(double) * 2 * n_m);
-  }
-  char* d = nullptr;
-  if (hipMalloc((void**)&d, in_bytes + h_out.size()) != hipSuccess) { (void)hipGetLastError(); return fail(c, BSGPU_ERR_DEVICE, "essential_ransac: out of device memory"); }
-  hipError_t e = hipMemcpyAsync(d, h_in.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    launch_essential_ransac(c->stream, n_sets, (const int*)d, (const double2*)(d + b_start + b_K), (const double2*)(d + b_start + b_K + b_px),
-                            (const double*)(d + b_start), prob, threshold_px, max_iters, seed, (unsigned char*)(d + in_bytes + out_E + out_i),
-                            (double*)(d + in_bytes), (int*)(d + in_bytes + out_E));
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d + in_bytes, h_out.size(), hipMemcpyDeviceToHost, c->stream);
-  const hipError_t e2 = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "essential_ransac: device error");
-  const double* oE = (const double*)h_out.data();
-  const int32_t* oi = (const int32_t*)(h_out.data() + out_E);
-  if (n_m) std::memcpy(mask, h_out.data() + out_E + out_i, n_m);
-  if (E) std::memcpy(E, oE, sizeof(double) * 9 * (size_t)n_sets);
-  for (int k = 0; k < n_sets; ++k) {
-    const int32_t* r = oi + (size_t)kRansacOutInts * k;
-    if (n_inliers) n_inliers[k] = r[0];
-    if (n_iters) n_iters[k] = r[1];
-    if (best_sample) std::memcpy(best_sample + 5 * (size_t)k, r + 2, 5 * sizeof(int32_t));
-    status[k] = r[7];
-  }
-  return BSGPU_OK;
-} catch (...) { return api_exception(c); }
-
-int bsgpu_absolute_pose_ransac(bsgpu_ctx* c, int32_t n_frames, const int32_t* obs_start, const double* pixels, const double* points,
-                               const int32_t* camera, double prob, double threshold_px, int32_t max_iters, uint64_t seed,
-                               int32_t truncate_pixels, uint8_t* mask, double* q_out, double* p_out, double* T_cam_world,
-                               int32_t* n_inliers, int32_t* n_iters, int32_t* best_sample, int32_t* status) try {
-  if (!c) return BSGPU_ERR_INVALID;
-  if (n_frames < 0 || !obs_start || !pixels || !points || !camera || !mask || !q_out || !p_out || !status)
-    return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: null argument");
-  if (!(prob >= 0.0 && prob < 1.0)) return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: prob must lie inside [0, 1)");
-  if (!(threshold_px > 0.0) || max_iters <= 0) return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: threshold_px and max_iters must be positive");
-  if (obs_start[0] != 0) return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: obs_start[0] must be 0");
-  for (int f = 0; f < n_frames; ++f) {
-    if (obs_start[f + 1] < obs_start[f]) return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: obs_start must be non-decreasing");
-    if (camera[f] < 0 || camera[f] >= (int)c->cams.size()) return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: camera index out of range");
-  }
-  for (int f = 0; f < n_frames; ++f)
-    if (obs_start[f + 1] - obs_start[f] > BSGPU_RANSAC_MAX_MATCHES)
-      return fail(c, BSGPU_ERR_UNSUPPORTED, "absolute_pose_ransac: a frame holds more than BSGPU_RANSAC_MAX_MATCHES pairs");
-  if (n_frames == 0) return BSGPU_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // one device buffer: inputs [obs_start | camera | cameras | pixels | points], outputs [per-frame doubles | per-frame ints | mask]
-  std::vector<DevCamera> cams(c->cams.size());
-  for (size_t i = 0; i < cams.size(); ++i) {
-    const bsgpu_camera& hc = c->cams[i];
-    cams[i].fx = hc.fx; cams[i].fy = hc.fy; cams[i].cx = hc.cx; cams[i].cy = hc.cy;
-    std::memcpy(cams[i].R, hc.R_cam_baselink, sizeof(cams[i].R));
-    std::memcpy(cams[i].t, hc.t_cam_baselink, sizeof(cams[i].t));
-  }
-  const size_t n_obs = (size_t)obs_start[n_frames];
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_start = al(sizeof(int32_t) * ((size_t)n_frames + 1)), b_cam = al(sizeof(int32_t) * (size_t)n_frames),
-               b_cams = al(sizeof(DevCamera) * cams.size()), b_pix = al(sizeof(double) * 2 * n_obs), b_pts = al(sizeof(double) * 3 * n_obs);
-  const size_t in_bytes = b_start + b_cam + b_cams + b_pix + b_pts;
-  const size_t out_d = al(sizeof(double) * kP3pOutDoubles * (size_t)n_frames), out_i = al(sizeof(int32_t) * kP3pOutInts * (size_t)n_frames),
-               out_m = al(n_obs);
-  std::vector<char> h_in(in_bytes), h_out(out_d + out_i + out_m);
-  const size_t o_cam = b_start, o_cams = o_cam + b_cam, o_pix = o_cams + b_cams, o_pts = o_pix + b_pix;
-  std::memcpy(h_in.data(), obs_start, sizeof(int32_t) * ((size_t)n_frames + 1));
-  std::memcpy(h_in.data() + o_cam, camera, sizeof(int32_t) * (size_t)n_frames);
-  std::memcpy(h_in.data() + o_cams, cams.data(), sizeof(DevCamera) * cams.size());
-  if (n_obs) {
-    std::memcpy(h_in.data() + o_pix, pixels, sizeof(double) * 2 * n_obs);
-    std::memcpy(h_in.data() + o_pts, points, sizeof(double) * 3 * n_obs);
-  }
-  char* d = nullptr;
-  if (hipMalloc((void**)&d, in_bytes + h_out.size()) != hipSuccess) { (void)hipGetLastError(); return fail(c, BSGPU_ERR_DEVICE, "absolute_pose_ransac: out of device memory"); }
-  hipError_t e = hipMemcpyAsync(d, h_in.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    launch_absolute_pose_ransac(c->stream, n_frames, (const int*)d, (const double2*)(d + o_pix), (const double*)(d + o_pts),
-                                (const DevCamera*)(d + o_cams), (const int*)(d + o_cam), prob, threshold_px, max_iters, seed,
-                                truncate_pixels != 0 ? 1 : 0, (unsigned char*)(d + in_bytes + out_d + out_i), (double*)(d + in_bytes),
-                                (int*)(d + in_bytes + out_d));
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), d + in_bytes, h_out.size(), hipMemcpyDeviceToHost, c->stream);
-  const hipError_t e2 = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "absolute_pose_ransac: device error");
-  const double* od = (const double*)h_out.data();
-  const int32_t* oi = (const int32_t*)(h_out.data() + out_d);
-  if (n_obs) std::memcpy(mask, h_out.data() + out_d + out_i, n_obs);
-  for (int f = 0; f < n_frames; ++f) {
-    const double* r = od + (size_t)kP3pOutDoubles * f;
-    const int32_t* ri = oi + (size_t)kP3pOutInts * f;
-    if (T_cam_world) std::memcpy(T_cam_world + 12 * (size_t)f, r, 12 * sizeof(double));
-    std::memcpy(q_out + 4 * (size_t)f, r + 12, 4 * sizeof(double));
-    std::memcpy(p_out + 3 * (size_t)f, r + 16, 3 * sizeof(double));
-    if (n_inliers) n_inliers[f] = ri[0];
-    if (n_iters) n_iters[f] = ri[1];
-    if (best_sample) std::memcpy(best_sample + 3 * (size_t)f, ri + 2, 3 * sizeof(int32_t));
-    status[f] = ri[5];
-  }
-  return BSGPU_OK;
-} catch (...) { return api_exception(c); }
-
-int bsgpu_relative_pose_ransac(bsgpu_ctx* c, int32_t n_sets, const int32_t* match_start, const double* px_first, const double* px_last,
-                               const int32_t* camera, double prob, double threshold_px, int32_t max_iters, uint64_t seed,
-                               int32_t truncate_pixels, double validate_px, double min_inlier_ratio, uint8_t* mask, double* T_last_first,
-                               double* q_out, double* p_out, double* points, uint8_t* valid_mask, double* inlier_ratio,
-                               int32_t* pair_valid, int32_t* n_inliers, int32_t* n_iters, int32_t* best_sample, int32_t* status) try {
-  if (!c) return BSGPU_ERR_INVALID;
-  if (n_sets < 0 || !match_start || !px_first || !px_last || !camera || !mask || !q_out || !p_out || !pair_valid || !status)
-    return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: null argument");
-  if (!(prob >= 0.0 && prob < 1.0)) return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: prob must lie inside [0, 1)");
-  if (!(threshold_px > 0.0) || !(validate_px > 0.0) || max_iters <= 0)
-    return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: threshold_px, validate_px and max_iters must be positive");
-  if (!(min_inlier_ratio >= 0.0 && min_inlier_ratio <= 1.0)) return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: min_inlier_ratio must lie inside [0, 1]");
-  if (match_start[0] != 0) return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: match_start[0] must be 0");
-  for (int k = 0; k < n_sets; ++k) {
-    if (match_start[k + 1] < match_start[k]) return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: match_start must be non-decreasing");
-    if (camera[k] < 0 || camera[k] >= (int)c->cams.size()) return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: camera index out of range");
-  }
-  for (int k = 0; k < n_sets; ++k)
-    if (match_start[k + 1] - match_start[k] > BSGPU_RANSAC_MAX_MATCHES)
-      return fail(c, BSGPU_ERR_UNSUPPORTED, "relative_pose_ransac: a set holds more than BSGPU_RANSAC_MAX_MATCHES matches");
-  if (n_sets == 0) return BSGPU_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  // one device buffer: inputs [match_start | camera | cameras | px_first | px_last], outputs [per-set doubles | per-set ints | points |
-  // mask | valid_mask]
-  std::vector<DevCamera> cams(c->cams.size());
-  for (size_t i = 0; i < cams.size(); ++i) {
-    const bsgpu_camera& hc = c->cams[i];
-    cams[i].fx = hc.fx; cams[i].fy = hc.fy; cams[i].cx = hc.cx; cams[i].cy = hc.cy;
-    std::memcpy(cams[i].R, hc.R_cam_baselink, sizeof(cams[i].R));
-    std::memcpy(cams[i].t, hc.t_cam_baselink, sizeof(cams[i].t));
-  }
-  const size_t n_m = (size_t)match_start[n_sets];
-  auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t b_start = al(sizeof(int32_t) * ((size_t)n_sets + 1)), b_cam = al(sizeof(int32_t) * (size_t)n_sets),
-               b_cams = al(sizeof(DevCamera) * cams.size()), b_px = al(sizeof(double) * 2 * n_m);
-  const size_t in_bytes = b_start + b_cam + b_cams + 2 * b_px;
-  const size_t out_d = al(sizeof(double) * kRelposeOutDoubles * (size_t)n_sets), out_i = al(sizeof(int32_t) * kRelposeOutInts * (size_t)n_sets),
-               out_p = al(sizeof(double) * 3 * n_m), out_m = al(n_m);
-  std::vector<char> h_in(in_bytes), h_out(out_d + out_i + out_p + 2 * out_m);
-  const size_t o_cam = b_start, o_cams = o_cam + b_cam, o_p0 = o_cams + b_cams, o_p1 = o_p0 + b_px;
-  std::memcpy(h_in.data(), match_start, sizeof(int32_t) * ((size_t)n_sets + 1));
-  std::memcpy(h_in.data() + o_cam, camera, sizeof(int32_t) * (size_t)n_sets);
-  std::memcpy(h_in.data() + o_cams, cams.data(), sizeof(DevCamera) * cams.size());
-  if (n_m) {
-    std::memcpy(h_in.data() + o_p0, px_first, sizeof(double) * 2 * n_m);
-    std::memcpy(h_in.data() + o_p1, px_last, sizeof(double) * 2 * n_m);
-  }
-  char* d = nullptr;
-  if (hipMalloc((void**)&d, in_bytes + h_out.size()) != hipSuccess) { (void)hipGetLastError(); return fail(c, BSGPU_ERR_DEVICE, "relative_pose_ransac: out of device memory"); }
-  char* dout = d + in_bytes;
-  hipError_t e = hipMemcpyAsync(d, h_in.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    launch_relative_pose_ransac(c->stream, n_sets, (const int*)d, (const double2*)(d + o_p0), (const double2*)(d + o_p1),
-                                (const DevCamera*)(d + o_cams), (const int*)(d + o_cam), prob, threshold_px, max_iters, seed,
-                                truncate_pixels != 0 ? 1 : 0, validate_px, min_inlier_ratio, (unsigned char*)(dout + out_d + out_i + out_p),
-                                (unsigned char*)(dout + out_d + out_i + out_p + out_m), (double*)(dout + out_d + out_i), (double*)dout,
-                                (int*)(dout + out_d));
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(h_out.data(), dout, h_out.size(), hipMemcpyDeviceToHost, c->stream);
-  const hipError_t e2 = hipStreamSynchronize(c->stream);
-  (void)hipFree(d);
-  if (e != hipSuccess || e2 != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "relative_pose_ransac: device error");
-  const double* od = (const double*)h_out.data();
-  const int32_t* oi = (const int32_t*)(h_out.data() + out_d);
-  if (n_m) {
-    std::memcpy(mask, h_out.data() + out_d + out_i + out_p, n_m);
-    if (valid_mask) std::memcpy(valid_mask, h_out.data() + out_d + out_i + out_p + out_m, n_m);
-    if (points) std::memcpy(points, h_out.data() + out_d + out_i, sizeof(double) * 3 * n_m);
-  }
-  for (int k = 0; k < n_sets; ++k) {
-    const double* r = od + (size_t)kRelposeOutDoubles * k;
-    const int32_t* ri = oi + (size_t)kRelposeOutInts * k;
-    if (T_last_first) std::memcpy(T_last_first + 12 * (size_t)k, r, 12 * sizeof(double));
-    std::memcpy(q_out + 8 * (size_t)k, r + 12, 8 * sizeof(double));
-    std::memcpy(p_out + 6 * (size_t)k, r + 20, 6 * sizeof(double));
-    if (inlier_ratio) inlier_ratio[k] = r[26];
-    if (n_inliers) n_inliers[k] = ri[0];
-    if (n_iters) n_iters[k] = ri[1];
-    if (best_sample) std::memcpy(best_sample + 7 * (size_t)k, ri + 2, 7 * sizeof(int32_t));
-    status[k] = ri[9];
-    pair_valid[k] = ri[10];
-  }
   return BSGPU_OK;
 } catch (...) { return api_exception(c); }
 

@@ -1,7 +1,8 @@
-// Host-side state of one libbsgpu context and the internal entry points of the three host translation units:
+// Host-side state of one libbsgpu context and the internal entry points of the host translation units:
 //   bsgpu_finalize.cpp  flattening of the described problem to device tables ([EXT] fuse HashGraph::createProblem)
 //   bsgpu_solve.cpp     the LM loop and its step ([EXT] ceres TrustRegionMinimizer + LevenbergMarquardtStrategy)
-//   bsgpu_api.cpp       the C-ABI of include/bsgpu.h
+//   bsgpu_api.cpp       the C-ABI of include/bsgpu.h: context, factors, solve, marginals, covariances, profiling hooks
+//   bsgpu_frontend.cpp  the C-ABI's front-end entry points (pre-integration, alignment, triangulation, localisation, the RANSACs)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -115,7 +116,7 @@ struct SlotMirror {
 
 }  // namespace bsg
 
-using namespace bsg;   // (internal header: included by the three host translation units only)
+using namespace bsg;   // (internal header: included by the host translation units only)
 
 struct bsgpu_ctx {
   int device = 0;
@@ -348,6 +349,20 @@ namespace bsg {
 inline void phase_mark(bsgpu_ctx* c, int phase) { if (c->prof_events) (void)hipEventRecord(c->prof_events[phase + 1], c->stream); }
 inline int fail(bsgpu_ctx* c, int code, const std::string& msg) { c->err = msg; return code; }
 int api_exception(bsgpu_ctx* c) noexcept;   // bsgpu_api.cpp: where every entry point's function-try-block ends
+// the caller's camera as the kernels read it, and the context's table of them
+inline DevCamera to_dev_camera(const bsgpu_camera& hc) {
+  DevCamera d;
+  d.fx = hc.fx; d.fy = hc.fy; d.cx = hc.cx; d.cy = hc.cy;
+  std::memcpy(d.R, hc.R_cam_baselink, sizeof(d.R));
+  std::memcpy(d.t, hc.t_cam_baselink, sizeof(d.t));
+  return d;
+}
+inline std::vector<DevCamera> dev_cameras(const bsgpu_ctx* c) {
+  std::vector<DevCamera> cams;
+  cams.reserve(c->cams.size());
+  for (const bsgpu_camera& hc : c->cams) cams.push_back(to_dev_camera(hc));
+  return cams;
+}
 
 #define HIPCHK(c, call)                                                                         \
   do { hipError_t e_ = (call); if (e_ != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_)); } while (0)

@@ -215,12 +215,7 @@ int finalize(bsgpu_ctx* c) {
   get_loss(BSGPU_LOSS_TRIVIAL, 1.0);
 
   // ---- camera table (online-calib factors fold their constant extrinsic blocks into derived cameras)
-  std::vector<DevCamera> cams;
-  for (const bsgpu_camera& hc : c->cams) {
-    DevCamera d; d.fx = hc.fx; d.fy = hc.fy; d.cx = hc.cx; d.cy = hc.cy;
-    std::memcpy(d.R, hc.R_cam_baselink, sizeof(d.R)); std::memcpy(d.t, hc.t_cam_baselink, sizeof(d.t));
-    cams.push_back(d);
-  }
+  std::vector<DevCamera> cams = dev_cameras(c);
   std::map<std::tuple<int, int, int>, int> derived_cam;
   // ---- online calibration: the extrinsic pair of the type-1 factors that is not constant (both blocks, or one of them).  Its derived camera
   // entries are rebuilt on the device before every evaluation (k_calib.hip), its tangent columns are a border of the reduced system.

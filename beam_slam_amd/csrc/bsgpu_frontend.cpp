@@ -1,0 +1,339 @@
+// The front-end entry points of the C-ABI (include/bsgpu.h): bsgpu_preintegrate, bsgpu_inertial_alignment, bsgpu_triangulate,
+// bsgpu_localize_frames and the three RANSACs.  Each checks its arguments, describes its arrays as a StageLayout (staging.h:
+// [inputs | outputs | scratch] in one device allocation), runs one kernel between one copy in and one copy out, and hands the
+// results to the caller's arrays: nothing is written to them unless the call succeeds.
+#include "bsgpu_ctx.h"
+#include "inertial_align.h"
+#include "staging.h"
+
+using namespace bsg;
+
+extern "C" {
+
+int bsgpu_preintegrate(int device, int32_t n, const int32_t* sample_start, const double* t, const double* w, const double* a,
+                       const double* t_end, const double* bg, const double* ba, const double* cov_w, const double* cov_a,
+                       const double* cov_bg, const double* cov_ba, double info_weight, double* consts_out) try {
+  if (n < 0) return BSGPU_ERR_INVALID;
+  if (n == 0) return BSGPU_OK;
+  if (!sample_start || !t_end || !bg || !ba || !cov_w || !cov_a || !cov_bg || !cov_ba || !consts_out) return BSGPU_ERR_INVALID;
+  // an interval may hold no samples (it stays the identity); the kernel indexes the samples by this table, so it is checked here
+  // (it may start above 0, so it is not check_start_table's)
+  if (sample_start[0] < 0) return BSGPU_ERR_INVALID;
+  for (int i = 0; i < n; ++i) if (sample_start[i + 1] < sample_start[i]) return BSGPU_ERR_INVALID;
+  const size_t ns = (size_t)sample_start[n], ni = (size_t)n;
+  if (ns > 0 && (!t || !w || !a)) return BSGPU_ERR_INVALID;
+  if (hipSetDevice(device) != hipSuccess) return BSGPU_ERR_DEVICE;
+  double covs[36];
+  std::memcpy(&covs[0], cov_w, 72); std::memcpy(&covs[9], cov_a, 72); std::memcpy(&covs[18], cov_bg, 72); std::memcpy(&covs[27], cov_ba, 72);
+  StageLayout L;
+  const int s_ss = L.in(sample_start, 4 * (ni + 1)), s_t = L.in(t, 8 * ns), s_w = L.in(w, 24 * ns), s_a = L.in(a, 24 * ns), s_te = L.in(t_end, 8 * ni),
+            s_bg = L.in(bg, 24 * ni), s_ba = L.in(ba, 24 * ni), s_cov = L.in(covs, sizeof(covs)), s_out = L.out(consts_out, 8 * 287 * ni);
+  DeviceStage D(L);
+  if (!D) return BSGPU_ERR_DEVICE;
+  const hipError_t e = D.run(nullptr, [&] {
+    launch_preintegrate(nullptr, n, D.ptr<int>(s_ss), D.ptr<double>(s_t), D.ptr<double>(s_w), D.ptr<double>(s_a), D.ptr<double>(s_te),
+                        D.ptr<double>(s_bg), D.ptr<double>(s_ba), D.ptr<double>(s_cov), info_weight, D.ptr<double>(s_out));
+  });
+  if (e != hipSuccess) { (void)hipGetLastError(); return BSGPU_ERR_DEVICE; }
+  L.scatter();
+  return BSGPU_OK;
+} catch (...) { return api_exception(nullptr); }
+
+int bsgpu_inertial_alignment(int device, int32_t n_paths, const int32_t* frame_start, const double* t_frame, const double* q_frame,
+                             const double* p_frame, const int32_t* imu_range, const double* t, const double* w, const double* a,
+                             int32_t bridge_gap, double min_excitation, int32_t apply_scale, double scale_min, double scale_max,
+                             double rank_tol, double* gravity, double* bg, double* scale, double* excitation, int32_t* gyro_rank,
+                             double* velocity, double* q_out, double* p_out, double* v_out, int32_t* status) try {
+  if (n_paths < 0) return BSGPU_ERR_INVALID;
+  if (n_paths == 0) return BSGPU_OK;
+  if (!frame_start || !imu_range || !gravity || !bg || !scale || !excitation || !gyro_rank || !status) return BSGPU_ERR_INVALID;
+  size_t ns = 0;
+  const auto range_ok = [&](int k) {
+    if (imu_range[2 * k] < 0 || imu_range[2 * k + 1] < imu_range[2 * k]) return false;
+    ns = std::max(ns, (size_t)imu_range[2 * k + 1]);
+    return true;
+  };
+  if (check_start_table(frame_start, n_paths, INT_MAX, range_ok) != kStartOk) return BSGPU_ERR_INVALID;
+  const size_t nf = (size_t)frame_start[n_paths], np = (size_t)n_paths;
+  if (nf > 0 && (!t_frame || !q_frame || !p_frame || !velocity || !q_out || !p_out || !v_out)) return BSGPU_ERR_INVALID;
+  if (ns > 0 && (!t || !w || !a)) return BSGPU_ERR_INVALID;
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return BSGPU_ERR_DEVICE; }
+  StageLayout L;
+  const int s_fs = L.in(frame_start, 4 * (np + 1)), s_rng = L.in(imu_range, 8 * np), s_tf = L.in(t_frame, 8 * nf), s_qf = L.in(q_frame, 32 * nf),
+            s_pf = L.in(p_frame, 24 * nf), s_t = L.in(t, 8 * ns), s_w = L.in(w, 24 * ns), s_a = L.in(a, 24 * ns);
+  const int s_g = L.out(gravity, 24 * np), s_bg = L.out(bg, 24 * np), s_sc = L.out(scale, 8 * np), s_ex = L.out(excitation, 8 * np),
+            s_rk = L.out(gyro_rank, 4 * np), s_st = L.out(status, 4 * np), s_vel = L.out(velocity, 24 * nf), s_qo = L.out(q_out, 32 * nf),
+            s_po = L.out(p_out, 24 * nf), s_vo = L.out(v_out, 24 * nf);
+  // the kernel's own working arrays (uninitialised): frame owners, per-frame and per-path doubles
+  const int s_own = L.scratch(4 * (nf + np)), s_fsc = L.scratch(8 * nf * kAlignFrameScratch), s_psc = L.scratch(8 * np * kAlignPathScratch);
+  DeviceStage D(L, 256);
+  if (!D) return BSGPU_ERR_DEVICE;
+  const auto F = [&](int s) { return D.ptr<double>(s); };
+  const auto I = [&](int s) { return D.ptr<int>(s); };
+  const hipError_t e = D.run(nullptr, [&] {
+    launch_inertial_alignment(nullptr, n_paths, I(s_fs), F(s_tf), F(s_qf), F(s_pf), I(s_rng), F(s_t), F(s_w), F(s_a), bridge_gap, min_excitation,
+                              apply_scale, scale_min, scale_max, rank_tol, F(s_g), F(s_bg), F(s_sc), F(s_ex), I(s_rk), F(s_vel), F(s_qo), F(s_po),
+                              F(s_vo), I(s_st), I(s_own), F(s_fsc), F(s_psc));
+  });
+  if (e != hipSuccess) { (void)hipGetLastError(); return BSGPU_ERR_DEVICE; }
+  L.scatter();
+  return BSGPU_OK;
+} catch (...) { return api_exception(nullptr); }
+
+int bsgpu_triangulate(bsgpu_ctx* c, int32_t n_tracks, const int32_t* track_start, const int32_t* q_block, const int32_t* p_block,
+                      const double* pixels, int32_t camera, int32_t truncate_pixels, double max_dist, double max_reproj, double* points,
+                      int32_t* status) try {
+  if (!c) return BSGPU_ERR_INVALID;
+  if (n_tracks < 0 || !track_start || !points || !status) return fail(c, BSGPU_ERR_INVALID, "null argument");
+  if (n_tracks == 0) return BSGPU_OK;
+  const int n_obs = track_start[n_tracks];
+  const StartCheck table = check_start_table(track_start, n_tracks);
+  if (table == kStartNotZero || n_obs < 0 || (n_obs > 0 && (!q_block || !p_block || !pixels)))
+    return fail(c, BSGPU_ERR_INVALID, "triangulate: malformed track table");
+  if (camera < 0 || camera >= (int)c->cams.size()) return fail(c, BSGPU_ERR_INVALID, "camera index out of range");
+  if (table == kStartDecreasing) return fail(c, BSGPU_ERR_INVALID, "triangulate: track_start must be non-decreasing");
+  std::vector<int32_t> pose_off((size_t)2 * n_obs);
+  for (int o = 0; o < n_obs; ++o) {
+    const int qb = q_block[o], pb = p_block[o];
+    if (qb < 0 || qb >= c->nb || pb < 0 || pb >= c->nb) return fail(c, BSGPU_ERR_INVALID, "triangulate: block out of range");
+    if (c->size[qb] != 4 || c->size[pb] != 3) return fail(c, BSGPU_ERR_INVALID, "triangulate: view blocks must be (orientation[4], position[3])");
+    pose_off[2 * (size_t)o] = c->off[qb];
+    pose_off[2 * (size_t)o + 1] = c->off[pb];
+  }
+  int rc = finalize(c);
+  if (rc != BSGPU_OK) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const DevCamera cam = to_dev_camera(c->cams[camera]);
+  const size_t nt = (size_t)n_tracks;
+  StageLayout L;
+  const int s_start = L.in(track_start, 4 * (nt + 1)), s_off = L.in(pose_off.data(), 8 * (size_t)n_obs), s_pix = L.in(pixels, 16 * (size_t)n_obs),
+            s_pts = L.out(points, 24 * nt), s_status = L.out(status, 4 * nt);
+  DeviceStage D(L);
+  if (!D) return fail(c, BSGPU_ERR_DEVICE, "triangulate: device error");
+  const hipError_t e = D.run(c->stream, [&] {
+    launch_triangulate(c->stream, n_tracks, D.ptr<int>(s_start), D.ptr<int2>(s_off), D.ptr<double2>(s_pix), c->d_x, cam,
+                       truncate_pixels != 0, max_dist, max_reproj, D.ptr<double>(s_pts), D.ptr<int>(s_status));
+  });
+  if (e != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "triangulate: device error");
+  L.scatter();
+  return BSGPU_OK;
+} catch (...) { return api_exception(c); }
+
+int bsgpu_localize_frames(bsgpu_ctx* c, int32_t n_frames, const int32_t* obs_start, const double* pixels, const double* points,
+                          const int32_t* lm_block, const int32_t* camera, const double* q_init, const double* p_init,
+                          int32_t loss_kind, double loss_a, double sqrt_info, int32_t truncate_pixels, int32_t min_points,
+                          int32_t image_width, int32_t image_height, const bsgpu_options* options, double* q_out, double* p_out,
+                          double* cov_out, double* avg_reproj, double* final_cost, int32_t* iterations, int32_t* status) try {
+  if (!c) return BSGPU_ERR_INVALID;
+  if (n_frames < 0 || !obs_start || !camera || !q_init || !p_init || !options || !q_out || !p_out || !status)
+    return fail(c, BSGPU_ERR_INVALID, "localize_frames: null argument");
+  if ((points == nullptr) == (lm_block == nullptr)) return fail(c, BSGPU_ERR_INVALID, "localize_frames: pass exactly one of points and lm_block");
+  if (options->trust_region_strategy_type != BSGPU_TR_LEVENBERG_MARQUARDT)
+    return fail(c, BSGPU_ERR_UNSUPPORTED, "localize_frames: its in-kernel loop is Levenberg-Marquardt only (trust_region_strategy_type must be 0)");
+  if (loss_kind < BSGPU_LOSS_TRIVIAL || loss_kind > BSGPU_LOSS_HUBER) return fail(c, BSGPU_ERR_INVALID, "unknown loss kind");
+  switch (check_start_table(obs_start, n_frames, INT_MAX, [&](int f) { return camera[f] >= 0 && camera[f] < (int)c->cams.size(); })) {
+    case kStartNotZero: return fail(c, BSGPU_ERR_INVALID, "localize_frames: obs_start[0] must be 0");
+    case kStartDecreasing: return fail(c, BSGPU_ERR_INVALID, "localize_frames: obs_start must be non-decreasing");
+    case kStartBadItem: return fail(c, BSGPU_ERR_INVALID, "camera index out of range");
+    default: break;
+  }
+  const size_t n_obs = (size_t)obs_start[n_frames], nf = (size_t)n_frames;
+  if (n_obs > 0 && !pixels) return fail(c, BSGPU_ERR_INVALID, "localize_frames: null pixels");
+  std::vector<int32_t> pt_off;
+  if (lm_block) {
+    if (!c->finalized || !c->d_x) return fail(c, BSGPU_ERR_INVALID, "localize_frames: lm_block needs the context's values on the device (finalize or solve first)");
+    pt_off.resize(n_obs);
+    for (size_t o = 0; o < n_obs; ++o) {
+      const int b = lm_block[o];
+      if (b < 0 || b >= c->nb) return fail(c, BSGPU_ERR_INVALID, "localize_frames: block out of range");
+      if (c->size[b] != 3 || c->manifold[b] != BSGPU_MANIFOLD_EUCLIDEAN) return fail(c, BSGPU_ERR_INVALID, "localize_frames: lm_block must name 3-d Euclidean blocks");
+      pt_off[o] = c->off[b];
+    }
+  }
+  if (n_frames == 0) return BSGPU_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const std::vector<DevCamera> cams = dev_cameras(c);
+  std::vector<double> pose(7 * nf);
+  for (size_t f = 0; f < nf; ++f) {
+    std::memcpy(&pose[7 * f], q_init + 4 * f, 4 * sizeof(double));
+    std::memcpy(&pose[7 * f + 4], p_init + 3 * f, 3 * sizeof(double));
+  }
+  StageLayout L;
+  const int s_start = L.in(obs_start, 4 * (nf + 1)), s_cam = L.in(camera, 4 * nf), s_off = L.in(pt_off.data(), 4 * pt_off.size()),
+            s_cams = L.in(cams.data(), sizeof(DevCamera) * cams.size()), s_pix = L.in(pixels, 16 * n_obs),
+            s_pts = L.in(points, points ? 24 * n_obs : 0), s_pose = L.in(pose.data(), 8 * pose.size());
+  // per-frame records, split below: kLocOutStride doubles and 2 ints (bsgpu_internal.h)
+  const int s_od = L.out(nullptr, 8 * kLocOutStride * nf), s_oi = L.out(nullptr, 4 * 2 * nf);
+  DeviceStage D(L);
+  if (!D) return fail(c, BSGPU_ERR_DEVICE, "localize_frames: out of device memory");
+  const hipError_t e = D.run(c->stream, [&] {
+    launch_localize(c->stream, n_frames, D.ptr<int>(s_start), D.ptr<double2>(s_pix), points ? D.ptr<double>(s_pts) : nullptr,
+                    lm_block ? D.ptr<int>(s_off) : nullptr, lm_block ? c->d_x : nullptr, D.ptr<DevCamera>(s_cams), D.ptr<int>(s_cam),
+                    D.ptr<double>(s_pose), loss_kind, loss_a, sqrt_info, truncate_pixels != 0 ? 1 : 0, min_points, image_width, image_height,
+                    *options, D.ptr<double>(s_od), D.ptr<int>(s_oi));
+  });
+  if (e != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "localize_frames: device error");
+  const double* od = L.out_image<double>(s_od);
+  const int32_t* oi = L.out_image<int32_t>(s_oi);
+  for (size_t f = 0; f < nf; ++f) {
+    const double* r = od + kLocOutStride * f;
+    std::memcpy(q_out + 4 * f, r, 4 * sizeof(double));
+    std::memcpy(p_out + 3 * f, r + 4, 3 * sizeof(double));
+    if (final_cost) final_cost[f] = r[7];
+    if (avg_reproj) avg_reproj[f] = r[8];
+    if (cov_out) std::memcpy(cov_out + 36 * f, r + 9, 36 * sizeof(double));
+    if (iterations) iterations[f] = oi[2 * f];
+    status[f] = oi[2 * f + 1];
+  }
+  return BSGPU_OK;
+} catch (...) { return api_exception(c); }
+
+int bsgpu_essential_ransac(bsgpu_ctx* c, int32_t n_sets, const int32_t* match_start, const double* px_prev, const double* px_cur,
+                           const double* K, double prob, double threshold_px, int32_t max_iters, uint64_t seed, uint8_t* mask, double* E,
+                           int32_t* n_inliers, int32_t* n_iters, int32_t* best_sample, int32_t* status) try {
+  if (!c) return BSGPU_ERR_INVALID;
+  if (n_sets < 0 || !match_start || !px_prev || !px_cur || !K || !mask || !status)
+    return fail(c, BSGPU_ERR_INVALID, "essential_ransac: null argument");
+  if (!(prob > 0.0 && prob < 1.0)) return fail(c, BSGPU_ERR_INVALID, "essential_ransac: prob must lie inside (0, 1)");
+  if (!(threshold_px > 0.0) || max_iters <= 0) return fail(c, BSGPU_ERR_INVALID, "essential_ransac: threshold_px and max_iters must be positive");
+  switch (check_start_table(match_start, n_sets, BSGPU_RANSAC_MAX_MATCHES, [&](int k) { return K[4 * (size_t)k] > 0.0 && K[4 * (size_t)k + 1] > 0.0; })) {
+    case kStartNotZero: return fail(c, BSGPU_ERR_INVALID, "essential_ransac: match_start[0] must be 0");
+    case kStartDecreasing: return fail(c, BSGPU_ERR_INVALID, "essential_ransac: match_start must be non-decreasing");
+    case kStartBadItem: return fail(c, BSGPU_ERR_INVALID, "essential_ransac: focal lengths must be positive");
+    case kStartTooLong: return fail(c, BSGPU_ERR_UNSUPPORTED, "essential_ransac: a set holds more than BSGPU_RANSAC_MAX_MATCHES matches");
+    case kStartOk: break;
+  }
+  if (n_sets == 0) return BSGPU_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t n_m = (size_t)match_start[n_sets], ns = (size_t)n_sets;
+  StageLayout L;
+  const int s_start = L.in(match_start, 4 * (ns + 1)), s_K = L.in(K, 32 * ns), s_p0 = L.in(px_prev, 16 * n_m), s_p1 = L.in(px_cur, 16 * n_m);
+  // per-set ints, split below: kRansacOutInts (bsgpu_internal.h)
+  const int s_E = L.out(E, 72 * ns), s_oi = L.out(nullptr, 4 * kRansacOutInts * ns), s_mask = L.out(mask, n_m);
+  DeviceStage D(L);
+  if (!D) return fail(c, BSGPU_ERR_DEVICE, "essential_ransac: out of device memory");
+  const hipError_t e = D.run(c->stream, [&] {
+    launch_essential_ransac(c->stream, n_sets, D.ptr<int>(s_start), D.ptr<double2>(s_p0), D.ptr<double2>(s_p1), D.ptr<double>(s_K), prob,
+                            threshold_px, max_iters, seed, D.ptr<unsigned char>(s_mask), D.ptr<double>(s_E), D.ptr<int>(s_oi));
+  });
+  if (e != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "essential_ransac: device error");
+  L.scatter();
+  const int32_t* oi = L.out_image<int32_t>(s_oi);
+  for (size_t k = 0; k < ns; ++k) {
+    const int32_t* r = oi + kRansacOutInts * k;
+    if (n_inliers) n_inliers[k] = r[0];
+    if (n_iters) n_iters[k] = r[1];
+    if (best_sample) std::memcpy(best_sample + 5 * k, r + 2, 5 * sizeof(int32_t));
+    status[k] = r[7];
+  }
+  return BSGPU_OK;
+} catch (...) { return api_exception(c); }
+
+int bsgpu_absolute_pose_ransac(bsgpu_ctx* c, int32_t n_frames, const int32_t* obs_start, const double* pixels, const double* points,
+                               const int32_t* camera, double prob, double threshold_px, int32_t max_iters, uint64_t seed,
+                               int32_t truncate_pixels, uint8_t* mask, double* q_out, double* p_out, double* T_cam_world,
+                               int32_t* n_inliers, int32_t* n_iters, int32_t* best_sample, int32_t* status) try {
+  if (!c) return BSGPU_ERR_INVALID;
+  if (n_frames < 0 || !obs_start || !pixels || !points || !camera || !mask || !q_out || !p_out || !status)
+    return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: null argument");
+  if (!(prob >= 0.0 && prob < 1.0)) return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: prob must lie inside [0, 1)");
+  if (!(threshold_px > 0.0) || max_iters <= 0) return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: threshold_px and max_iters must be positive");
+  switch (check_start_table(obs_start, n_frames, BSGPU_RANSAC_MAX_MATCHES, [&](int f) { return camera[f] >= 0 && camera[f] < (int)c->cams.size(); })) {
+    case kStartNotZero: return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: obs_start[0] must be 0");
+    case kStartDecreasing: return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: obs_start must be non-decreasing");
+    case kStartBadItem: return fail(c, BSGPU_ERR_INVALID, "absolute_pose_ransac: camera index out of range");
+    case kStartTooLong: return fail(c, BSGPU_ERR_UNSUPPORTED, "absolute_pose_ransac: a frame holds more than BSGPU_RANSAC_MAX_MATCHES pairs");
+    case kStartOk: break;
+  }
+  if (n_frames == 0) return BSGPU_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const std::vector<DevCamera> cams = dev_cameras(c);
+  const size_t n_obs = (size_t)obs_start[n_frames], nf = (size_t)n_frames;
+  StageLayout L;
+  const int s_start = L.in(obs_start, 4 * (nf + 1)), s_cam = L.in(camera, 4 * nf), s_cams = L.in(cams.data(), sizeof(DevCamera) * cams.size()),
+            s_pix = L.in(pixels, 16 * n_obs), s_pts = L.in(points, 24 * n_obs);
+  // per-frame records, split below: kP3pOutDoubles and kP3pOutInts (bsgpu_internal.h)
+  const int s_od = L.out(nullptr, 8 * kP3pOutDoubles * nf), s_oi = L.out(nullptr, 4 * kP3pOutInts * nf), s_mask = L.out(mask, n_obs);
+  DeviceStage D(L);
+  if (!D) return fail(c, BSGPU_ERR_DEVICE, "absolute_pose_ransac: out of device memory");
+  const hipError_t e = D.run(c->stream, [&] {
+    launch_absolute_pose_ransac(c->stream, n_frames, D.ptr<int>(s_start), D.ptr<double2>(s_pix), D.ptr<double>(s_pts),
+                                D.ptr<DevCamera>(s_cams), D.ptr<int>(s_cam), prob, threshold_px, max_iters, seed, truncate_pixels != 0 ? 1 : 0,
+                                D.ptr<unsigned char>(s_mask), D.ptr<double>(s_od), D.ptr<int>(s_oi));
+  });
+  if (e != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "absolute_pose_ransac: device error");
+  L.scatter();
+  const double* od = L.out_image<double>(s_od);
+  const int32_t* oi = L.out_image<int32_t>(s_oi);
+  for (size_t f = 0; f < nf; ++f) {
+    const double* r = od + kP3pOutDoubles * f;
+    const int32_t* ri = oi + kP3pOutInts * f;
+    if (T_cam_world) std::memcpy(T_cam_world + 12 * f, r, 12 * sizeof(double));
+    std::memcpy(q_out + 4 * f, r + 12, 4 * sizeof(double));
+    std::memcpy(p_out + 3 * f, r + 16, 3 * sizeof(double));
+    if (n_inliers) n_inliers[f] = ri[0];
+    if (n_iters) n_iters[f] = ri[1];
+    if (best_sample) std::memcpy(best_sample + 3 * f, ri + 2, 3 * sizeof(int32_t));
+    status[f] = ri[5];
+  }
+  return BSGPU_OK;
+} catch (...) { return api_exception(c); }
+
+int bsgpu_relative_pose_ransac(bsgpu_ctx* c, int32_t n_sets, const int32_t* match_start, const double* px_first, const double* px_last,
+                               const int32_t* camera, double prob, double threshold_px, int32_t max_iters, uint64_t seed,
+                               int32_t truncate_pixels, double validate_px, double min_inlier_ratio, uint8_t* mask, double* T_last_first,
+                               double* q_out, double* p_out, double* points, uint8_t* valid_mask, double* inlier_ratio,
+                               int32_t* pair_valid, int32_t* n_inliers, int32_t* n_iters, int32_t* best_sample, int32_t* status) try {
+  if (!c) return BSGPU_ERR_INVALID;
+  if (n_sets < 0 || !match_start || !px_first || !px_last || !camera || !mask || !q_out || !p_out || !pair_valid || !status)
+    return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: null argument");
+  if (!(prob >= 0.0 && prob < 1.0)) return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: prob must lie inside [0, 1)");
+  if (!(threshold_px > 0.0) || !(validate_px > 0.0) || max_iters <= 0)
+    return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: threshold_px, validate_px and max_iters must be positive");
+  if (!(min_inlier_ratio >= 0.0 && min_inlier_ratio <= 1.0)) return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: min_inlier_ratio must lie inside [0, 1]");
+  switch (check_start_table(match_start, n_sets, BSGPU_RANSAC_MAX_MATCHES, [&](int k) { return camera[k] >= 0 && camera[k] < (int)c->cams.size(); })) {
+    case kStartNotZero: return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: match_start[0] must be 0");
+    case kStartDecreasing: return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: match_start must be non-decreasing");
+    case kStartBadItem: return fail(c, BSGPU_ERR_INVALID, "relative_pose_ransac: camera index out of range");
+    case kStartTooLong: return fail(c, BSGPU_ERR_UNSUPPORTED, "relative_pose_ransac: a set holds more than BSGPU_RANSAC_MAX_MATCHES matches");
+    case kStartOk: break;
+  }
+  if (n_sets == 0) return BSGPU_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  const std::vector<DevCamera> cams = dev_cameras(c);
+  const size_t n_m = (size_t)match_start[n_sets], ns = (size_t)n_sets;
+  StageLayout L;
+  const int s_start = L.in(match_start, 4 * (ns + 1)), s_cam = L.in(camera, 4 * ns), s_cams = L.in(cams.data(), sizeof(DevCamera) * cams.size()),
+            s_p0 = L.in(px_first, 16 * n_m), s_p1 = L.in(px_last, 16 * n_m);
+  // per-set records, split below: kRelposeOutDoubles and kRelposeOutInts (bsgpu_internal.h)
+  const int s_od = L.out(nullptr, 8 * kRelposeOutDoubles * ns), s_oi = L.out(nullptr, 4 * kRelposeOutInts * ns), s_pts = L.out(points, 24 * n_m),
+            s_mask = L.out(mask, n_m), s_valid = L.out(valid_mask, n_m);
+  DeviceStage D(L);
+  if (!D) return fail(c, BSGPU_ERR_DEVICE, "relative_pose_ransac: out of device memory");
+  const hipError_t e = D.run(c->stream, [&] {
+    launch_relative_pose_ransac(c->stream, n_sets, D.ptr<int>(s_start), D.ptr<double2>(s_p0), D.ptr<double2>(s_p1),
+                                D.ptr<DevCamera>(s_cams), D.ptr<int>(s_cam), prob, threshold_px, max_iters, seed, truncate_pixels != 0 ? 1 : 0,
+                                validate_px, min_inlier_ratio, D.ptr<unsigned char>(s_mask), D.ptr<unsigned char>(s_valid),
+                                D.ptr<double>(s_pts), D.ptr<double>(s_od), D.ptr<int>(s_oi));
+  });
+  if (e != hipSuccess) return fail(c, BSGPU_ERR_DEVICE, "relative_pose_ransac: device error");
+  L.scatter();
+  const double* od = L.out_image<double>(s_od);
+  const int32_t* oi = L.out_image<int32_t>(s_oi);
+  for (size_t k = 0; k < ns; ++k) {
+    const double* r = od + kRelposeOutDoubles * k;
+    const int32_t* ri = oi + kRelposeOutInts * k;
+    if (T_last_first) std::memcpy(T_last_first + 12 * k, r, 12 * sizeof(double));
+    std::memcpy(q_out + 8 * k, r + 12, 8 * sizeof(double));
+    std::memcpy(p_out + 6 * k, r + 20, 6 * sizeof(double));
+    if (inlier_ratio) inlier_ratio[k] = r[26];
+    if (n_inliers) n_inliers[k] = ri[0];
+    if (n_iters) n_iters[k] = ri[1];
+    if (best_sample) std::memcpy(best_sample + 7 * k, ri + 2, 7 * sizeof(int32_t));
+    status[k] = ri[9];
+    pair_valid[k] = ri[10];
+  }
+  return BSGPU_OK;
+} catch (...) { return api_exception(c); }
+
+}  // extern "C"
