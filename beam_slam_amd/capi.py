@@ -115,7 +115,7 @@ SYMBOLS = [
     "reprojection_errors", "preintegrate", "triangulate", "time_reproj_jacobian_ms", "reproj_jacobian_bytes", "dense_solve", "plan_info",
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
     "covariance_requests", "localize_frames", "num_factorizations", "essential_ransac", "absolute_pose_ransac",
-    "relative_pose_ransac", "inertial_alignment",
+    "relative_pose_ransac", "inertial_alignment", "register_scans", "register_scans_error",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -139,6 +139,13 @@ ALIGN_OK, ALIGN_TOO_FEW_FRAMES, ALIGN_BAD_IMU, ALIGN_NOT_EXCITED, ALIGN_RANK_DEF
 ALIGN_MIN_EXCITATION, ALIGN_SCALE_MIN, ALIGN_SCALE_MAX, ALIGN_RANK_TOL = 0.25, 0.02, 1.0, 1e-10
 INERTIAL_ALIGNMENT_ARGTYPES = [C.c_int, C.c_int32, _ip, _dp, _dp, _dp, _ip, _dp, _dp, _dp, C.c_int32, C.c_double, C.c_int32, C.c_double,
                                C.c_double, C.c_double, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _ip]
+#: bsgpu_register_scans: per-pair status values (the first convergence criterion that fired), the limits, the reference's shipped ICP
+#: parameters (config/matchers/icp.json; rotation_threshold and rel_mse_eps: PCL's defaults, recalled) and the typed prototype
+ICP_MAX_ITERATIONS, ICP_TRANSFORM, ICP_ABS_MSE, ICP_REL_MSE, ICP_TOO_FEW_CORRESPONDENCES = 1, 2, 3, 4, 5
+ICP_MAX_CELLS, ICP_MAX_ITER = 1 << 22, 1000
+ICP_DEFAULTS = dict(max_corr=1.0, max_iter=50, t_eps=1e-8, fit_eps=1e-2, rotation_threshold=0.99999, rel_mse_eps=1e-5)
+REGISTER_SCANS_ARGTYPES = [C.c_int, C.c_int32, _ip, _dp, _ip, _dp, _dp, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double,
+                           C.c_double, _dp, _dp, _dp, _ip, _ip, _ip]
 
 
 def _ptr(a, typ):

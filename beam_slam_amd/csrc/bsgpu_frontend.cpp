@@ -1,12 +1,21 @@
-// The front-end entry points of the C-ABI (include/bsgpu.h): bsgpu_preintegrate, bsgpu_inertial_alignment, bsgpu_triangulate,
-// bsgpu_localize_frames and the three RANSACs.  Each checks its arguments, describes its arrays as a StageLayout (staging.h:
+// The front-end entry points of the C-ABI (include/bsgpu.h): bsgpu_preintegrate, bsgpu_inertial_alignment, bsgpu_register_scans,
+// bsgpu_triangulate, bsgpu_localize_frames and the three RANSACs.  Each checks its arguments, describes its arrays as a StageLayout (staging.h:
 // [inputs | outputs | scratch] in one device allocation), runs one kernel between one copy in and one copy out, and hands the
 // results to the caller's arrays: nothing is written to them unless the call succeeds.
+#include <algorithm>
+#include <cmath>
+#include <string>
+
 #include "bsgpu_ctx.h"
+#include "icp.h"
 #include "inertial_align.h"
 #include "staging.h"
 
 using namespace bsg;
+
+namespace {
+thread_local std::string g_register_scans_error;   // what this thread's last failed bsgpu_register_scans objected to (it has no context to keep it)
+}
 
 extern "C" {
 
@@ -79,6 +88,108 @@ int bsgpu_inertial_alignment(int device, int32_t n_paths, const int32_t* frame_s
   L.scatter();
   return BSGPU_OK;
 } catch (...) { return api_exception(nullptr); }
+
+const char* bsgpu_register_scans_error(void) { return g_register_scans_error.c_str(); }
+
+int bsgpu_register_scans(int device, int32_t n_pairs, const int32_t* ref_start, const double* ref_points, const int32_t* tgt_start,
+                         const double* tgt_points, const double* T_init, double max_corr, int32_t max_iter, double t_eps, double fit_eps,
+                         double rotation_threshold, double rel_mse_eps, double* T_refest_ref, double* T_ref_tgt, double* mse,
+                         int32_t* n_corr, int32_t* n_iters, int32_t* status) try {
+  const auto refuse = [](int code, const char* why) { g_register_scans_error = why; return code; };
+  if (n_pairs < 0 || !ref_start || !tgt_start || !T_refest_ref || !status) return refuse(BSGPU_ERR_INVALID, "register_scans: null argument");
+  if (!(max_corr > 0.0) || !std::isfinite(max_corr)) return refuse(BSGPU_ERR_INVALID, "register_scans: max_corr must be positive and finite");
+  if (max_iter < 1) return refuse(BSGPU_ERR_INVALID, "register_scans: max_iter must be at least 1");
+  if (!(t_eps >= 0.0) || !(fit_eps >= 0.0) || !(rel_mse_eps >= 0.0) || rotation_threshold != rotation_threshold)
+    return refuse(BSGPU_ERR_INVALID, "register_scans: t_eps, fit_eps and rel_mse_eps must not be negative, no tolerance NaN");
+  if (max_iter > BSGPU_ICP_MAX_ITER) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans: max_iter exceeds BSGPU_ICP_MAX_ITER");
+  // the two start tables, in check_start_table's order; an item is bad when one of its points is not finite (a NaN would choose a grid cell)
+  const auto finite_items = [](const int32_t* start, const double* pts) {
+    return [start, pts](int k) {
+      if (start[k + 1] > start[k] && !pts) return false;
+      for (size_t i = 3 * (size_t)start[k]; i < 3 * (size_t)start[k + 1]; ++i) if (!std::isfinite(pts[i])) return false;
+      return true;
+    };
+  };
+  switch (check_start_table(ref_start, n_pairs, INT_MAX, finite_items(ref_start, ref_points))) {
+    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "register_scans: ref_start[0] must be 0");
+    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "register_scans: ref_start must be non-decreasing");
+    case kStartBadItem: return refuse(BSGPU_ERR_INVALID, "register_scans: null or non-finite reference points");
+    default: break;
+  }
+  switch (check_start_table(tgt_start, n_pairs, INT_MAX, finite_items(tgt_start, tgt_points))) {
+    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "register_scans: tgt_start[0] must be 0");
+    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "register_scans: tgt_start must be non-decreasing");
+    case kStartBadItem: return refuse(BSGPU_ERR_INVALID, "register_scans: null or non-finite target points");
+    default: break;
+  }
+  const size_t np = (size_t)n_pairs;
+  static const double eye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  std::vector<double> init(12 * np);
+  for (size_t i = 0; i < init.size(); ++i) {
+    init[i] = T_init ? T_init[i] : eye[i % 12];
+    if (!std::isfinite(init[i])) return refuse(BSGPU_ERR_INVALID, "register_scans: non-finite T_init");
+  }
+  // the grids: the bounding box of every target cloud under its T_init, by the arithmetic the device will use (icp.h)
+  std::vector<IcpGrid> grids(np);
+  std::vector<int32_t> chunk_start(np + 1, 0);
+  double cells = 0.0;
+  int max_targets = 0, max_chunks = 0;
+  for (size_t p = 0; p < np; ++p) {
+    IcpGrid& g = grids[p];
+    g.h = max_corr; g.cell0 = (int)cells;
+    for (int a = 0; a < 3; ++a) { g.o[a] = 0.0; g.n[a] = 0; }
+    const int n = tgt_start[p + 1] - tgt_start[p], chunks = (ref_start[p + 1] - ref_start[p] + kIcpChunk - 1) / kIcpChunk;
+    chunk_start[p + 1] = chunk_start[p] + chunks;
+    max_targets = std::max(max_targets, n); max_chunks = std::max(max_chunks, chunks);
+    if (n == 0) continue;
+    double lo[3], hi[3], q[3];
+    for (int i = 0; i < n; ++i) {
+      icp_apply(&init[12 * p], tgt_points + 3 * ((size_t)tgt_start[p] + i), q);
+      for (int a = 0; a < 3; ++a) { lo[a] = i == 0 || q[a] < lo[a] ? q[a] : lo[a]; hi[a] = i == 0 || q[a] > hi[a] ? q[a] : hi[a]; }
+    }
+    double nc[3], here = 1.0;
+    for (int a = 0; a < 3; ++a) {
+      if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return refuse(BSGPU_ERR_INVALID, "register_scans: T_init takes a target point out of range");
+      nc[a] = icp_axis_cells(lo[a], hi[a], max_corr);
+      here *= nc[a];
+    }
+    if (!(here <= (double)BSGPU_ICP_MAX_CELLS)) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans: a pair's grid exceeds BSGPU_ICP_MAX_CELLS cells");
+    cells += here;
+    if (cells > 16.0 * BSGPU_ICP_MAX_CELLS) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans: the call's grids exceed 16 x BSGPU_ICP_MAX_CELLS cells");
+    for (int a = 0; a < 3; ++a) { g.o[a] = lo[a]; g.n[a] = (int)nc[a]; }
+  }
+  if (n_pairs == 0) return BSGPU_OK;
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "register_scans: hipSetDevice failed"); }
+  const size_t n_ref = (size_t)ref_start[n_pairs], n_tgt = (size_t)tgt_start[n_pairs], n_chunks = (size_t)chunk_start[n_pairs];
+  const int n_tiles = (int)(((size_t)cells + kIcpScanTile - 1) / kIcpScanTile);
+  StageLayout L;
+  const int s_rs = L.in(ref_start, 4 * (np + 1)), s_ref = L.in(ref_points, 24 * n_ref), s_ts = L.in(tgt_start, 4 * (np + 1)),
+            s_tgt = L.in(tgt_points, 24 * n_tgt), s_ti = L.in(init.data(), 96 * np), s_cs = L.in(chunk_start.data(), 4 * (np + 1)),
+            s_gr = L.in(grids.data(), sizeof(IcpGrid) * np);
+  const int s_T = L.out(T_refest_ref, 96 * np), s_Trt = L.out(T_ref_tgt, 96 * np), s_mse = L.out(mse, 8 * np), s_nc = L.out(n_corr, 4 * np),
+            s_ni = L.out(n_iters, 4 * np), s_st = L.out(status, 4 * np);
+  // the kernels' working arrays (uninitialised: the launch clears the cells, icp_prepare_kernel sets the per-pair words): the transformed targets and their
+  // cells, the grids' cells and their tile sums, the sorted records, the partial records, mse_prev and the done words
+  const int s_tq = L.scratch(24 * n_tgt), s_tc = L.scratch(4 * n_tgt), s_cells = L.scratch(4 * (size_t)n_tiles * kIcpScanTile),
+            s_tile = L.scratch(4 * (size_t)n_tiles), s_rec = L.scratch(32 * n_tgt), s_part = L.scratch(8 * kIcpRec * n_chunks),
+            s_prev = L.scratch(8 * np), s_done = L.scratch(4 * np);
+  DeviceStage D(L);
+  if (!D) return refuse(BSGPU_ERR_DEVICE, "register_scans: out of device memory");
+  const IcpParams P{max_iter, t_eps, fit_eps, rotation_threshold, rel_mse_eps};
+  const auto F = [&](int s) { return D.ptr<double>(s); };
+  const auto I = [&](int s) { return D.ptr<int>(s); };
+  const hipError_t e = D.run(nullptr, [&] {
+    launch_register_scans(nullptr, n_pairs, max_targets, (int)n_tgt, max_chunks, n_tiles, I(s_rs), F(s_ref), I(s_ts), F(s_tgt), F(s_ti), I(s_cs),
+                          D.ptr<IcpGrid>(s_gr), max_corr, P, F(s_T), F(s_Trt), F(s_mse), I(s_nc), I(s_ni), I(s_st), F(s_tq), I(s_tc), I(s_cells),
+                          I(s_tile), F(s_rec), F(s_part), F(s_prev), I(s_done));
+  });
+  if (e != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "register_scans: device error"); }
+  L.scatter();
+  return BSGPU_OK;
+} catch (...) {
+  try { g_register_scans_error = "register_scans: out of host memory"; } catch (...) {}
+  return api_exception(nullptr);
+}
 
 int bsgpu_triangulate(bsgpu_ctx* c, int32_t n_tracks, const int32_t* track_start, const int32_t* q_block, const int32_t* p_block,
                       const double* pixels, int32_t camera, int32_t truncate_pixels, double max_dist, double max_reproj, double* points,

@@ -547,6 +547,17 @@ void launch_inertial_alignment(hipStream_t s, int n_paths, const int* frame_star
                                int bridge_gap, double min_excitation, int apply_scale, double scale_min, double scale_max, double rank_tol,
                                double* gravity, double* bg, double* scale, double* excitation, int* gyro_rank, double* velocity,
                                double* q_out, double* p_out, double* v_out, int* status, int* own, double* fs, double* ps);
+// ICP scan registration (k_icp.hip, bsgpu_register_scans): a pair over many workgroups.  Inputs as the C-ABI's, on the device, plus
+// what the host derives: chunk_start (n_pairs + 1: a pair's partial records, one per kIcpChunk source points), grids (per pair, icp.h).
+// Scratch: tq 3 / tcell 1 per target, cells n_tiles x kIcpScanTile ints (every pair's grid cells, padded to whole tiles),
+// tile_sum n_tiles, rec 4 per target, part kIcpRec per chunk, mse_prev / done 1 per pair.
+struct IcpGrid; struct IcpParams;
+constexpr int kIcpScanTile = 1024;
+void launch_register_scans(hipStream_t s, int n_pairs, int max_targets, int n_targets, int max_chunks, int n_tiles, const int* ref_start,
+                           const double* ref, const int* tgt_start, const double* tgt, const double* T_init, const int* chunk_start,
+                           const IcpGrid* grids, double max_corr, const IcpParams& P, double* T, double* T_ref_tgt, double* mse, int* n_corr,
+                           int* n_iters, int* status, double* tq, int* tcell, int* cells, int* tile_sum, double* rec, double* part,
+                           double* mse_prev, int* done);
 void launch_triangulate(hipStream_t s, int n_tracks, const int* track_start, const int2* pose_off, const double2* pix, const double* x,
                         const DevCamera& cam, bool truncate, double max_dist, double max_reproj, double* points, int* status);
 // frame localisation (k_loc.hip, bsgpu_localize_frames): one workgroup per frame; pts (3 per observation) or pt_off (offset of the

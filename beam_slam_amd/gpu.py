@@ -104,6 +104,47 @@ def inertial_alignment(frame_start, t_frame, q_frame, p_frame, imu_range, t, w, 
     return out
 
 
+def register_scans(ref_start, ref_points, tgt_start, tgt_points, T_init=None, max_corr=capi.ICP_DEFAULTS["max_corr"],
+                   max_iter=capi.ICP_DEFAULTS["max_iter"], t_eps=capi.ICP_DEFAULTS["t_eps"], fit_eps=capi.ICP_DEFAULTS["fit_eps"],
+                   rotation_threshold=capi.ICP_DEFAULTS["rotation_threshold"], rel_mse_eps=capi.ICP_DEFAULTS["rel_mse_eps"], device=0):
+    """bsgpu_register_scans: point-to-point ICP (the reference's matcher in its shipped ICP configuration) for a batch of scan pairs.
+    Pair p registers the reference cloud ref_points[ref_start[p]:ref_start[p+1]] onto the target cloud
+    tgt_points[tgt_start[p]:tgt_start[p+1]] (moved by T_init[p], 3 x 4, first when given).  Returns a dict of arrays: T_refest_ref and
+    T_ref_tgt (P x 3 x 4), mse, n_corr, n_iters, status (P)."""
+    import numpy as np
+    rs = np.ascontiguousarray(ref_start, np.int32).reshape(-1)
+    ts = np.ascontiguousarray(tgt_start, np.int32).reshape(-1)
+    rp = np.ascontiguousarray(ref_points, np.float64).reshape(-1, 3)
+    tp = np.ascontiguousarray(tgt_points, np.float64).reshape(-1, 3)
+    P = rs.size - 1
+    ti = None if T_init is None else np.ascontiguousarray(T_init, np.float64).reshape(-1, 3, 4)
+    if P < 0 or ts.size != P + 1 or (ti is not None and ti.shape[0] != P):
+        raise capi.SolverError(capi.ERR_INVALID, "register_scans: array sizes do not agree")
+    if int(rs.max()) > rp.shape[0] or int(ts.max()) > tp.shape[0]:
+        raise capi.SolverError(capi.ERR_INVALID, "register_scans: ref_start / tgt_start name more points than were passed")
+    out = dict(T_refest_ref=np.zeros((P, 3, 4)), T_ref_tgt=np.zeros((P, 3, 4)), mse=np.zeros(P), n_corr=np.zeros(P, np.int32),
+               n_iters=np.zeros(P, np.int32), status=np.zeros(P, np.int32))
+    fn = lib().bsgpu_register_scans
+    fn.argtypes = capi.REGISTER_SCANS_ARGTYPES
+    _dp, _ip = capi._dp, capi._ip
+    d = lambda x: None if x is None else x.ctypes.data_as(_dp)
+    i = lambda x: x.ctypes.data_as(_ip)
+    rc = fn(device, P, i(rs), d(rp), i(ts), d(tp), d(ti), float(max_corr), int(max_iter), float(t_eps), float(fit_eps),
+            float(rotation_threshold), float(rel_mse_eps), d(out["T_refest_ref"]), d(out["T_ref_tgt"]), d(out["mse"]), i(out["n_corr"]),
+            i(out["n_iters"]), i(out["status"]))
+    if rc != 0:
+        raise capi.SolverError(rc, register_scans_error())
+    return out
+
+
+def register_scans_error():
+    """What this thread's last failed bsgpu_register_scans objected to."""
+    fn = lib().bsgpu_register_scans_error
+    fn.restype = ctypes.c_char_p
+    fn.argtypes = []
+    return fn().decode()
+
+
 class GpuSolver(capi.Solver):
     """One bsgpu context on HIP device `device`."""
 

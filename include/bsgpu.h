@@ -533,6 +533,44 @@ int bsgpu_inertial_alignment(int device, int32_t n_paths, const int32_t* frame_s
                              double rank_tol, double* gravity, double* bg, double* scale, double* excitation, int32_t* gyro_rank,
                              double* velocity, double* q_out, double* p_out, double* v_out, int32_t* status);
 
+/* Point-to-point ICP scan registration for a batch of scan pairs — the matcher_->Match() of MultiScanRegistration::MatchScans
+ * (bs_models/src/lib/scan_registration/multi_scan_registration.cpp:451-487; the same call in ScanToMapRegistration, in
+ * RelocCandidateSearchScanContext::AlignSubmapsFromScanMatches and in submap_alignment.cpp) in the shipped ICP configuration
+ * (config/matchers/icp.json: max_corr 1, max_iter 50, t_eps 1e-8, fit_eps 1e-2, res 0, multiscale_steps 0).  [EXT] libbeam's
+ * IcpMatcher and PCL's IterativeClosestPoint are not in the reference checkout: the algorithm below is RECALLED, not verified, and it
+ * is computed in FP64 where PCL computes in float.
+ * Pair p: the reference cloud S = ref_points[3 ref_start[p] .. 3 ref_start[p+1]) (SetRef, PCL's source) and the target cloud
+ * tgt_points[3 tgt_start[p] ..) (SetTarget), both packed xyz; T_init (optional, 12 doubles per pair, row-major 3 x 4:
+ * T_LidarRefEst_LidarTgt of :454) is applied to the target on the device first (pcl::transformPointCloud of :462), giving Q; NULL is the
+ * identity.  T = I; iteration k = 1 .. max_iter:
+ *   correspondences   s_i = T S_i; j(i) the nearest point of Q by squared distance in FP64, ties to the lowest target index; kept iff
+ *                     d^2 <= max_corr^2.  Fewer than 3 kept: status TOO_FEW_CORRESPONDENCES, T stays as it was.
+ *   step              rigid Kabsch / Umeyama without scale over the kept (s_i, Q_j(i)): centroids, 3 x 3 cross-covariance, the rotation
+ *                     from its SVD with the determinant fix (a cross-covariance of rank < 2: no rotation), T <- dT T.
+ *   convergence       (PCL's DefaultConvergenceCriteria, recalled) the first that fires: k >= max_iter: MAX_ITERATIONS (counts as
+ *                     converged, as in PCL); 1/2 (tr dR - 1) >= rotation_threshold and |dt|^2 <= t_eps: TRANSFORM;
+ *                     |mse - mse_prev| < fit_eps: ABS_MSE; |mse - mse_prev| / mse_prev < rel_mse_eps: REL_MSE.  mse: the mean of the kept
+ *                     SQUARED distances of this iteration; mse_prev starts at +infinity.
+ * The nearest neighbour is found through a dense grid over Q's bounding box with cell edge max_corr; the search is exact.  A pair
+ * whose grid would have more than BSGPU_ICP_MAX_CELLS cells, a call whose grids together would have more than 16 times as many, or
+ * max_iter > BSGPU_ICP_MAX_ITER: UNSUPPORTED.  The sums over the correspondences have a fixed order (chunks of source points), so a
+ * pair's results never depend on the other pairs of the call, bit for bit.
+ * Outputs per pair: T_refest_ref (12: the matcher's result, maps S onto Q: T_RefEst_Ref of :474); T_ref_tgt (optional, 12:
+ * inv(T_refest_ref) T_init, :475 T_LIDARREF_LIDARTGT); mse, n_corr (optional: of the last iteration; mse 0 when nothing was kept);
+ * n_iters (optional: steps applied); status (BSGPU_ICP_*; converged unless TOO_FEW_CORRESPONDENCES).  n_pairs == 0 does nothing; an
+ * empty cloud gives TOO_FEW_CORRESPONDENCES.  INVALID: NULL where an array is needed, a start table that does not begin at 0 or
+ * decreases, a non-finite point or T_init entry, max_corr not positive and finite, max_iter < 1, a negative or NaN tolerance.
+ * Nothing is written unless the call succeeds; bsgpu_register_scans_error says what this thread's last failed call objected to.  */
+enum { BSGPU_ICP_MAX_ITERATIONS = 1, BSGPU_ICP_TRANSFORM = 2, BSGPU_ICP_ABS_MSE = 3, BSGPU_ICP_REL_MSE = 4,
+       BSGPU_ICP_TOO_FEW_CORRESPONDENCES = 5 };
+#define BSGPU_ICP_MAX_CELLS (1 << 22)
+#define BSGPU_ICP_MAX_ITER 1000
+int bsgpu_register_scans(int device, int32_t n_pairs, const int32_t* ref_start, const double* ref_points, const int32_t* tgt_start,
+                         const double* tgt_points, const double* T_init, double max_corr, int32_t max_iter, double t_eps,
+                         double fit_eps, double rotation_threshold, double rel_mse_eps, double* T_refest_ref, double* T_ref_tgt,
+                         double* mse, int32_t* n_corr, int32_t* n_iters, int32_t* status);
+const char* bsgpu_register_scans_error(void);
+
 /* Landmark triangulation for a batch of feature tracks at the context's CURRENT values (after a solve: the values the
  * solve left on the device) — VisualOdometry::TriangulateLandmark (bs_models/src/visual_odometry.cpp:532-610) and
  * SLAMInitialization::TriangulateLandmark (bs_models/src/slam_initialization.cpp:699-701), i.e. the [EXT]

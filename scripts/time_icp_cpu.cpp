@@ -1,0 +1,51 @@
+// CPU context for scripts/time_register_scans.py: wall time of icp.h's serial loop (icp_register_serial: grid build and iterations, pair
+// after pair) on one core.  Input: <reps> then a binary file of doubles holding the pairs in the format of tests/plan/test_icp.cpp's
+// command 1.  Output: reps lines MS <milliseconds for all pairs>, then ITERS <per pair> and STATUS <per pair>.
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "icp.h"
+
+struct Pair { std::vector<double> S, Q, Ti; double h; bsg::IcpParams P; double max_cells; };
+
+int main(int argc, char** argv) {
+  if (argc < 3) return 2;
+  const int reps = std::atoi(argv[1]);
+  std::FILE* f = std::fopen(argv[2], "rb");
+  if (!f) return 2;
+  auto rd = [&](double* v, size_t n) { return n == 0 || std::fread(v, sizeof(double), n, f) == n; };
+  std::vector<Pair> pairs;
+  double kind;
+  while (rd(&kind, 1)) {
+    double h[10];
+    if (kind != 1.0 || !rd(h, 10) || h[0] < 0 || h[1] < 0) return 3;
+    Pair p;
+    p.S.resize(3 * (size_t)h[0]); p.Q.resize(3 * (size_t)h[1]); p.Ti.resize(h[2] != 0.0 ? 12 : 0);
+    if (!rd(p.S.data(), p.S.size()) || !rd(p.Q.data(), p.Q.size()) || !rd(p.Ti.data(), p.Ti.size())) return 3;
+    p.h = h[3]; p.P = bsg::IcpParams{(int)h[4], h[5], h[6], h[7], h[8]}; p.max_cells = h[9];
+    pairs.push_back(p);
+  }
+  std::fclose(f);
+  std::vector<int> iters(pairs.size()), status(pairs.size());
+  for (int r = 0; r < reps + 1; ++r) {
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t k = 0; k < pairs.size(); ++k) {
+      const Pair& p = pairs[k];
+      double T[12], Trt[12], mse;
+      int n_corr;
+      if (!bsg::icp_register_serial((int)(p.S.size() / 3), p.S.data(), (int)(p.Q.size() / 3), p.Q.data(), p.Ti.empty() ? nullptr : p.Ti.data(), p.h,
+                                    p.P, p.max_cells, T, Trt, &mse, &n_corr, &iters[k], &status[k]))
+        return 5;
+    }
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (r > 0) std::printf("MS %.6f\n", ms);
+  }
+  std::printf("ITERS");
+  for (int v : iters) std::printf(" %d", v);
+  std::printf("\nSTATUS");
+  for (int v : status) std::printf(" %d", v);
+  std::printf("\n");
+  return 0;
+}
