@@ -115,7 +115,7 @@ SYMBOLS = [
     "reprojection_errors", "preintegrate", "triangulate", "time_reproj_jacobian_ms", "reproj_jacobian_bytes", "dense_solve", "plan_info",
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
     "covariance_requests", "localize_frames", "num_factorizations", "essential_ransac", "absolute_pose_ransac",
-    "relative_pose_ransac", "inertial_alignment", "register_scans", "register_scans_error",
+    "relative_pose_ransac", "inertial_alignment", "register_scans", "register_scans_error", "backsub_tangent_table",
 ]
 
 _dp = C.POINTER(C.c_double)

@@ -990,6 +990,33 @@ int bsgpu_reprojection_errors(bsgpu_ctx* c, double* err) try {
   return BSGPU_OK;
 } catch (...) { return api_exception(c); }
 
+int bsgpu_backsub_tangent_table(bsgpu_ctx* c, int32_t* fac_t, int32_t* joined) try {
+  if (!c) return BSGPU_ERR_INVALID;
+  if (!fac_t || !joined) return fail(c, BSGPU_ERR_INVALID, "null argument");
+  int rc = finalize(c);
+  if (rc != BSGPU_OK) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const Visual& V = c->vis;
+  if ((rc = ensure_vis_src(c)) != BSGPU_OK) return rc;
+  if (V.n == 0) return BSGPU_OK;
+  std::vector<int2> ft(V.n);
+  std::vector<int> cam_pose(V.n), cp_tq(V.n_cam_pose), cp_tp(V.n_cam_pose);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(ft.data(), V.fac_t, sizeof(int2) * V.n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(cam_pose.data(), V.cam_pose, sizeof(int) * V.n, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(cp_tq.data(), V.cp_tq, sizeof(int) * V.n_cam_pose, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(cp_tp.data(), V.cp_tp, sizeof(int) * V.n_cam_pose, hipMemcpyDeviceToHost));
+  const int n0 = c->groups[BSGPU_F_REPROJ].n;
+  for (int i = 0; i < V.n; ++i) {
+    const int t = c->vis_src[i] >> 28, f = c->vis_src[i] & ((1 << 28) - 1);
+    const size_t o = 2 * (size_t)((t == BSGPU_F_REPROJ ? 0 : n0) + f);
+    if (cam_pose[i] < 0 || cam_pose[i] >= V.n_cam_pose) return fail(c, BSGPU_ERR_DEVICE, "backsub_tangent_table: camera-pose id out of range");
+    fac_t[o] = ft[i].x; fac_t[o + 1] = ft[i].y;
+    joined[o] = cp_tq[cam_pose[i]]; joined[o + 1] = cp_tp[cam_pose[i]];
+  }
+  return BSGPU_OK;
+} catch (...) { return api_exception(c); }
+
 double bsgpu_time_reproj_jacobian_ms(bsgpu_ctx* c, int32_t reps) {
   if (!c) return -1.0;
   if (finalize(c) != BSGPU_OK || c->vis.n == 0 || reps <= 0) return -1.0;

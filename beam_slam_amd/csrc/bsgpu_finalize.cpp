@@ -560,7 +560,9 @@ int finalize(bsgpu_ctx* c) {
     V.cost_part = c->alloc<double>(V.n_cost_part);
     V.cost_part_cand = c->alloc<double>(V.n_cost_part);
     V.mcc_part = c->alloc<double>(std::max(1, backsub_mcc_groups(V)));
-    if (!V.J || !V.CR || !V.r) return fail(c, BSGPU_ERR_DEVICE, "out of device memory (visual tables)");
+    V.fac_t = c->alloc<int2>(nv);
+    if (!V.J || !V.CR || !V.r || !V.fac_t) return fail(c, BSGPU_ERR_DEVICE, "out of device memory (visual tables)");
+    launch_fac_t(c->stream, V);   // (both flattenings leave cam_pose, cp_tq and cp_tp queued on the stream)
     if (c->calib.on) {
       c->calib.E = c->alloc<double>((size_t)std::max(1, nv) * 12); c->calib.Et = c->alloc<double>((size_t)std::max(1, nv) * 12);
       c->calib.part = c->alloc<double>((size_t)std::max(1, calib_border_blocks(V)) * kCalibPartStride);

@@ -131,6 +131,8 @@ struct Visual {
   int n_cam_pose = 0;
   int* cp_tq = nullptr;       // camera pose -> tangent offset of q (or -1)
   int* cp_tp = nullptr;
+  int2* fac_t = nullptr;      // factor -> (cp_tq, cp_tp) of its camera pose: the back-substitution's tangent offsets without the hop through cam_pose
+                              // (written by launch_fac_t at the end of every flattening, host or device: finalize())
   // pair segments
   int n_seg = 0, n_ent = 0;
   int* seg_ci = nullptr; int* seg_cj = nullptr; int* seg_start = nullptr;
@@ -363,6 +365,7 @@ struct DenseDev {
 struct BatchArgTable {
   std::vector<unsigned char> host;
   size_t stride = 0, lds = 0;
+  bool lds_over = false;   // (backsub_mcc: a window's pose step does not fit the staging limit — the launch gathers from memory)
   int max_grid = 0;
   void* dev = nullptr;
   template <class A> void push(const A& a) {
@@ -658,6 +661,7 @@ void launch_spcg_finish(hipStream_t s, int T, const double* x, const int* iperm,
 int pcg_done_slot();
 int pcg_iters_slot();
 int backsub_mcc_groups(const Visual& v);   // workgroups (= model-cost partials) of launch_backsub_mcc
+void launch_fac_t(hipStream_t s, const Visual& v);   // Visual::fac_t = (cp_tq, cp_tp)[cam_pose]
 // (marg / marg_part: the model-cost terms of the window's dense prior as further workgroups of the launch; returns whether they were carried)
 bool launch_backsub_mcc(hipStream_t s, const Visual& v, int n_pose, const double* y_pose, double* delta, double* mcc_part,
                         const SmallGroupSet* small = nullptr, int n_small_units = 0, const UpdateRide* upd = nullptr, const MargDev* marg = nullptr,

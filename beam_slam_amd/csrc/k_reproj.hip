@@ -572,38 +572,202 @@ void launch_pairs(hipStream_t s, const Visual& v, double* S, int ld, int rhs_row
 // TrustRegionMinimizer) with J d = -(A y_cam + B y_l): the rows are still in L1 and a launch of its own is saved.  Factors whose
 // landmark is constant (f >= n_elim) are handled one per lane by the workgroups after the landmark ones.
 // ---------------------------------------------------------------------------------------------------
-BSG_DEV void pose_part(const double* __restrict__ Jf_row, int tq, int tp, const double* __restrict__ y_pose, double& j0, double& j1) {
-  // (the 96-byte row as six 16-byte pieces instead of twelve 8-byte loads)
-  const double2* J2 = reinterpret_cast<const double2*>(Jf_row);
-  const double2 v0 = J2[0], v1 = J2[1], v2 = J2[2], v3 = J2[3], v4 = J2[4], v5 = J2[5];
-  const double Jf[12] = {v0.x, v0.y, v1.x, v1.y, v2.x, v2.y, v3.x, v3.y, v4.x, v4.y, v5.x, v5.y};
-  j0 = 0.0; j1 = 0.0;
-  if (tq >= 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { const double yv = y_pose[tq + k]; j0 += Jf[k] * yv; j1 += Jf[6 + k] * yv; }
-  }
-  if (tp >= 0) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { const double yv = y_pose[tp + k]; j0 += Jf[3 + k] * yv; j1 += Jf[9 + k] * yv; }
+// The pose step y_cam, staged in the launch's dynamic LDS when it fits (backsub_stage_bytes): a landmark workgroup's first loads are then its
+// ranges and this copy, independent of each other, and the gathers behind the rows are LDS reads instead of one more trip to memory.
+extern __shared__ __attribute__((aligned(16))) double bsg_backsub_y[];
+// (32 KB: with the 32 bytes of the sums, four workgroups per compute unit — what the kernel's registers allow — still fit the 160 KB)
+constexpr int kBacksubStageMax = 4096;
+static size_t backsub_stage_bytes(int n_pose) {   // (2, 4 or 8 pieces of 16 bytes per thread: backsub_stage_y)
+  if (n_pose <= 0 || n_pose > kBacksubStageMax) return 0;
+  const int n2 = (n_pose + 1) >> 1;
+  return (size_t)4096 * (n2 <= 512 ? 2 : n2 <= 1024 ? 4 : 8);
+}
+template <bool Y_LDS> BSG_DEV double backsub_y(const double* __restrict__ y_pose, int i) {
+  if constexpr (Y_LDS) return bsg_backsub_y[i]; else return y_pose[i];
+}
+// the pose row of factor f in 16-byte pieces (the full layout's 96 bytes: [theta0 t0 | theta1 t1]; the compact one's 48: [theta0 | theta1]) ...
+template <bool COMPACT> BSG_DEV void pose_row_load(const double* __restrict__ J, int f, double (&A)[COMPACT ? 6 : 12]) {
+  if constexpr (COMPACT) {
+    const double2* J2 = reinterpret_cast<const double2*>(J + (size_t)f * kJACompact);
+    const double2 v0 = J2[0], v1 = J2[1], v2 = J2[2];
+    A[0] = v0.x; A[1] = v0.y; A[2] = v1.x; A[3] = v1.y; A[4] = v2.x; A[5] = v2.y;
+  } else {
+    const double2* J2 = reinterpret_cast<const double2*>(J + (size_t)f * kJAStride);
+    const double2 v0 = J2[0], v1 = J2[1], v2 = J2[2], v3 = J2[3], v4 = J2[4], v5 = J2[5];
+    A[0] = v0.x; A[1] = v0.y; A[2] = v1.x; A[3] = v1.y; A[4] = v2.x; A[5] = v2.y;
+    A[6] = v3.x; A[7] = v3.y; A[8] = v4.x; A[9] = v4.y; A[10] = v5.x; A[11] = v5.y;
   }
 }
-// ... of the compact layout (Visual::ja == kJACompact): the row holds [theta row 0 | theta row 1], the translation columns are the negated
-// landmark part B of the same factor, which every caller has loaded (-b y adds with the bits of t y: negation is exact)
-BSG_DEV void pose_part_compact(const double* __restrict__ Jf_row, const double (&B)[6], int tq, int tp, const double* __restrict__ y_pose, double& j0, double& j1) {
-  const double2* J2 = reinterpret_cast<const double2*>(Jf_row);
-  const double2 v0 = J2[0], v1 = J2[1], v2 = J2[2];
-  const double Jf[6] = {v0.x, v0.y, v1.x, v1.y, v2.x, v2.y};
+// ... and A y_cam from it.  The compact layout's translation columns are the negated landmark part B of the same factor, which every caller
+// has loaded (-b y adds with the bits of t y: negation is exact).  tq, tp: the tangent offsets of the factor's q and p blocks (-1: constant).
+template <bool Y_LDS, bool COMPACT>
+BSG_DEV void pose_row_dot(const double (&A)[COMPACT ? 6 : 12], const double (&B)[6], int tq, int tp, const double* __restrict__ y_pose, double& j0, double& j1) {
   j0 = 0.0; j1 = 0.0;
-  if (tq >= 0) {
+  if constexpr (COMPACT) {
+    if (tq >= 0) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { const double yv = y_pose[tq + k]; j0 += Jf[k] * yv; j1 += Jf[3 + k] * yv; }
-  }
-  if (tp >= 0) {
+      for (int k = 0; k < 3; ++k) { const double yv = backsub_y<Y_LDS>(y_pose, tq + k); j0 += A[k] * yv; j1 += A[3 + k] * yv; }
+    }
+    if (tp >= 0) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { const double yv = y_pose[tp + k]; j0 += (-B[k]) * yv; j1 += (-B[3 + k]) * yv; }
+      for (int k = 0; k < 3; ++k) { const double yv = backsub_y<Y_LDS>(y_pose, tp + k); j0 += (-B[k]) * yv; j1 += (-B[3 + k]) * yv; }
+    }
+  } else {
+    if (tq >= 0) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { const double yv = backsub_y<Y_LDS>(y_pose, tq + k); j0 += A[k] * yv; j1 += A[6 + k] * yv; }
+    }
+    if (tp >= 0) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { const double yv = backsub_y<Y_LDS>(y_pose, tp + k); j0 += A[3 + k] * yv; j1 += A[9 + k] * yv; }
+    }
   }
 }
-__device__ __forceinline__ void backsub_mcc_kernel_body(const int bsg_bx, const int bsg_gx, int n_lm, int n_lm_groups, int n_elim, int n, const int* __restrict__ lm_start, const double* __restrict__ J, int ja, const double* __restrict__ JB, const double2* __restrict__ r, const double* __restrict__ CR, const int* __restrict__ cam_pose, const int* __restrict__ cp_tq, const int* __restrict__ cp_tp, const double* __restrict__ Linv, const double* __restrict__ z, int n_pose, const double* __restrict__ y_pose, double* __restrict__ delta, double* __restrict__ mcc_part, int n_vis_blocks, const SmallGroupSet& small, int n_small_units, const UpdateRide& up, int first_update_block) {
+// the copy: 16-byte pieces — the buffer is a whole number of 256-byte units —, K per thread, all asked for before the first is stored; a thread past the end
+// copies the last piece to a place of its own (backsub_stage_bytes rounds the request up to K x 4 KB), so that nothing here is conditional.  They
+// are back with the landmark's range, and stored before the rows are asked for: the copy's registers are free again by then.
+template <int K> BSG_DEV void backsub_stage_y(const double* __restrict__ y_pose, int n2) {
+  const double2* y2 = reinterpret_cast<const double2*>(y_pose);
+  double2* s2 = reinterpret_cast<double2*>(bsg_backsub_y);
+  double2 ys[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) { const int i = (int)threadIdx.x + 256 * k; ys[k] = y2[i < n2 ? i : n2 - 1]; }
+#pragma unroll
+  for (int k = 0; k < K; ++k) s2[(int)threadIdx.x + 256 * k] = ys[k];
+}
+// Loaded values the compiler must have asked for HERE: a load whose only use sits behind a test of another load's value (the pose row behind
+// "tq >= 0") is otherwise moved down to that use, and is one more dependent trip.
+template <int N> BSG_DEV void pin(double (&a)[N]) {
+#pragma unroll
+  for (int k = 0; k + 1 < N; k += 2) asm volatile("" : "+v"(a[k]), "+v"(a[k + 1]));
+}
+BSG_DEV void pin(double2& a, int2& b) { asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(b.x), "+v"(b.y)); }
+BSG_DEV void row6_load(const double* __restrict__ base, int pitch, int f, double (&R)[6]) {
+  const double2* p = reinterpret_cast<const double2*>(base + (size_t)f * pitch);
+  const double2 a = p[0], b = p[1], c = p[2];
+  R[0] = a.x; R[1] = a.y; R[2] = b.x; R[3] = b.y; R[4] = c.x; R[5] = c.y;
+}
+// The landmark workgroups.  In a window without C rows and with the compact pose part (the large windows: Visual::no_cr, ::ja) a lane's dependent chain has
+// two trips to memory: (1) the landmark's range, with its Linv and z and the copy of y_cam; (2) everything the lane's first two factors need in
+// EITHER pass — the B row, the pose row, the tangent offsets (Visual::fac_t) and r, which only the second pass uses — asked for together, the second
+// factor's at the first's address when there is none.  The full layout asks for the second factor behind the first, and with C rows the second
+// pass loads B (see R below).  A lane's third and later factor (a track of 17 views or more) goes round the loop as before and loads again in
+// the second pass.  Every sum keeps its operands and its order.
+template <bool Y_LDS, bool COMPACT>
+BSG_DEV void backsub_lm_group(const int bsg_bx, int n_lm, const int* __restrict__ lm_start, const double* __restrict__ J, const double* __restrict__ JB, const double2* __restrict__ r, const double* __restrict__ CR, const int2* __restrict__ fac_t, const double* __restrict__ Linv, const double* __restrict__ z, int n_pose, const double* __restrict__ y_pose, double* __restrict__ delta, const UpdateRide& up, double& acc, double& upd_d2, double& upd_x2) {
+  const int gid = bsg_bx * 256 + threadIdx.x;
+  const int l = gid >> 3, sub = gid & 7;
+  const bool valid = l < n_lm;
+  int beg = 0, end = 0;
+  if (valid) { beg = lm_start[l]; end = lm_start[l + 1]; }
+  // (what depends on the landmark alone is asked for with its range, not after the sums below: two trips off the dependent path)
+  const int lc = valid ? l : 0;
+  const double* Li = Linv + (size_t)lc * kLmRec;
+  const double Li0 = Li[0], Li1 = Li[1], Li2 = Li[2], Li3 = Li[3], Li4 = Li[4], Li5 = Li[5];
+  const double* zl = z + (size_t)lc * kLmRec;
+  const double zl0 = zl[0], zl1 = zl[1], zl2 = zl[2];
+  if constexpr (Y_LDS) {
+    const int n2 = (n_pose + 1) >> 1;
+    if (n2 <= 512) backsub_stage_y<2>(y_pose, n2); else if (n2 <= 1024) backsub_stage_y<4>(y_pose, n2); else backsub_stage_y<8>(y_pose, n2);
+  }
+  // (no C rows — Visual::no_cr: the sums are taken with the B rows, sum_a B_a^T (A_a y), and C^T = Linv B^T is applied to them once per landmark below)
+  const bool no_cr = COMPACT || CR == nullptr;   // (compact implies no C rows: C is the B row)
+  constexpr int kA = COMPACT ? 6 : 12;
+  const int f0 = beg + sub;
+  const bool h0 = f0 < end, h1 = f0 + 8 < end;
+  // (a lane without a first or second factor asks for row 0 instead, or its first again — every table has a row 0, were it an empty table's
+  // allocation unit — and leaves what comes back unused: the requests are unconditional and leave together)
+  const int f0c = h0 ? f0 : 0, f1 = h1 ? f0 + 8 : f0c;
+  // R: the row the first pass multiplies with — C, or B where no C rows are kept.  In the compact layout (always B) the second pass has it in registers;
+  // in the full one it loads B as it did: with the 96-byte pose rows, rows held across the sums take the kernel past the 128 registers of four
+  // waves per SIMD.  With the rows of the first pass comes r, which only the second reads.  Both factors at once in the compact layout, 112 bytes
+  // each; in the full one — 160 bytes — the second factor's are asked for behind the first's sums, for the same registers' sake.
+  double A0[kA], A1[kA], R0[6], R1[6];
+  int2 t0 = fac_t[f0c];
+  pose_row_load<COMPACT>(J, f0c, A0);
+  if (no_cr) row6_load(JB, 6, f0c, R0); else row6_load(CR, 8, f0c, R0);
+  double2 r0 = r[f0c];
+  int2 t1 = t0;
+  double2 r1 = r0;
+  if constexpr (COMPACT) { t1 = fac_t[f1]; pose_row_load<true>(J, f1, A1); row6_load(JB, 6, f1, R1); r1 = r[f1]; pin(A1); pin(R1); pin(r1, t1); }
+  else {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) R1[k] = R0[k];
+  }
+  pin(A0); pin(R0); pin(r0, t0);
+  if constexpr (Y_LDS) __syncthreads();
+  double a0 = 0, a1 = 0, a2 = 0;
+  // (A y_cam of the lane's first two factors stays in registers for the second pass)
+  double jk0[2] = {0.0, 0.0}, jk1[2] = {0.0, 0.0};
+  if (h0) {
+    pose_row_dot<Y_LDS, COMPACT>(A0, R0, t0.x, t0.y, y_pose, jk0[0], jk1[0]);
+    a0 += R0[0] * jk0[0] + R0[3] * jk1[0]; a1 += R0[1] * jk0[0] + R0[4] * jk1[0]; a2 += R0[2] * jk0[0] + R0[5] * jk1[0];
+    if (h1) {
+      if constexpr (!COMPACT) {
+        t1 = fac_t[f1]; pose_row_load<false>(J, f1, A0); r1 = r[f1];   // (the first factor's pose row is done with)
+        if (no_cr) row6_load(JB, 6, f1, R1); else row6_load(CR, 8, f1, R1);
+        pin(A0); pin(r1, t1);
+        pose_row_dot<Y_LDS, false>(A0, R1, t1.x, t1.y, y_pose, jk0[1], jk1[1]);
+      } else pose_row_dot<Y_LDS, true>(A1, R1, t1.x, t1.y, y_pose, jk0[1], jk1[1]);
+      a0 += R1[0] * jk0[1] + R1[3] * jk1[1]; a1 += R1[1] * jk0[1] + R1[4] * jk1[1]; a2 += R1[2] * jk0[1] + R1[5] * jk1[1];
+    }
+  }
+  for (int f = f0 + 16; f < end; f += 8) {
+    double C[6], A[kA];
+    if (no_cr) row6_load(JB, 6, f, C); else row6_load(CR, 8, f, C);
+    const int2 t = fac_t[f];
+    pose_row_load<COMPACT>(J, f, A);
+    double j0, j1;
+    pose_row_dot<Y_LDS, COMPACT>(A, C, t.x, t.y, y_pose, j0, j1);
+    a0 += C[0] * j0 + C[3] * j1; a1 += C[1] * j0 + C[4] * j1; a2 += C[2] * j0 + C[5] * j1;
+  }
+#pragma unroll
+  for (int o = 4; o > 0; o >>= 1) { a0 += __shfl_xor(a0, o, 8); a1 += __shfl_xor(a1, o, 8); a2 += __shfl_xor(a2, o, 8); }
+  if (no_cr) {   // a <- Linv a   (Linv lower triangular: Li0 | Li1 Li2 | Li3 Li4 Li5)
+    const double b0 = a0, b1 = a1, b2 = a2;
+    a0 = Li0 * b0; a1 = Li1 * b0 + Li2 * b1; a2 = Li3 * b0 + Li4 * b1 + Li5 * b2;
+  }
+  if (!valid) return;
+  // (every one of the 8 lanes holds the sums)
+  const double w0 = zl0 - a0, w1 = zl1 - a1, w2 = zl2 - a2;
+  // y = Linv^T w
+  const double y0 = Li0 * w0 + Li1 * w1 + Li3 * w2;
+  const double y1 = Li2 * w1 + Li4 * w2;
+  const double y2 = Li5 * w2;
+  if (sub == 0) {
+    const int to = n_pose + 3 * l;
+    delta[to] = -y0; delta[to + 1] = -y1; delta[to + 2] = -y2;
+    if (up.n_blocks > 0) {   // the landmark's candidate and its terms of the step / x norms
+      const int xo = up.lm_xoff[l];
+      const double x0 = up.x[xo], x1 = up.x[xo + 1], x2v = up.x[xo + 2];
+      const double c0 = x0 + (-y0), c1 = x1 + (-y1), c2 = x2v + (-y2);
+      up.x_cand[xo] = c0; up.x_cand[xo + 1] = c1; up.x_cand[xo + 2] = c2;
+      const double e0 = x0 - c0, e1 = x1 - c1, e2 = x2v - c2;
+      upd_d2 = e0 * e0 + e1 * e1 + e2 * e2; upd_x2 = x0 * x0 + x1 * x1 + x2v * x2v;
+    }
+  }
+  if (h0) {
+    if constexpr (!COMPACT) { row6_load(JB, 6, f0, R0); if (h1) row6_load(JB, 6, f1, R1); }
+    const double d0 = -(jk0[0] + R0[0] * y0 + R0[1] * y1 + R0[2] * y2), d1 = -(jk1[0] + R0[3] * y0 + R0[4] * y1 + R0[5] * y2);
+    acc -= d0 * (r0.x + 0.5 * d0) + d1 * (r0.y + 0.5 * d1);
+  }
+  if (h1) {
+    const double d0 = -(jk0[1] + R1[0] * y0 + R1[1] * y1 + R1[2] * y2), d1 = -(jk1[1] + R1[3] * y0 + R1[4] * y1 + R1[5] * y2);
+    acc -= d0 * (r1.x + 0.5 * d0) + d1 * (r1.y + 0.5 * d1);
+  }
+  for (int f = f0 + 16; f < end; f += 8) {
+    double Bf[6], A[kA];
+    row6_load(JB, 6, f, Bf);
+    const int2 t = fac_t[f];
+    pose_row_load<COMPACT>(J, f, A);
+    double j0, j1;
+    pose_row_dot<Y_LDS, COMPACT>(A, Bf, t.x, t.y, y_pose, j0, j1);
+    const double d0 = -(j0 + Bf[0] * y0 + Bf[1] * y1 + Bf[2] * y2), d1 = -(j1 + Bf[3] * y0 + Bf[4] * y1 + Bf[5] * y2);
+    const double2 rf = r[f];
+    acc -= d0 * (rf.x + 0.5 * d0) + d1 * (rf.y + 0.5 * d1);
+  }
+}
+__device__ __forceinline__ void backsub_mcc_kernel_body(const int bsg_bx, const int bsg_gx, int n_lm, int n_lm_groups, int n_elim, int n, const int* __restrict__ lm_start, const double* __restrict__ J, int ja, const double* __restrict__ JB, const double2* __restrict__ r, const double* __restrict__ CR, const int2* __restrict__ fac_t, const double* __restrict__ Linv, const double* __restrict__ z, int n_pose, const double* __restrict__ y_pose, int y_lds, double* __restrict__ delta, double* __restrict__ mcc_part, int n_vis_blocks, const SmallGroupSet& small, int n_small_units, const UpdateRide& up, int first_update_block) {
   __shared__ double sred[4];
   if (up.n_blocks > 0 && bsg_bx >= first_update_block) {
     // the candidate of every block but the Euclidean landmarks (those: below, by the lanes that compute their step): the pose step is
@@ -625,82 +789,21 @@ __device__ __forceinline__ void backsub_mcc_kernel_body(const int bsg_bx, const 
   }
   double acc = 0.0, upd_d2 = 0.0, upd_x2 = 0.0;
   if (bsg_bx < n_lm_groups) {
-    const int gid = bsg_bx * 256 + threadIdx.x;
-    const int l = gid >> 3, sub = gid & 7;
-    const bool valid = l < n_lm;
-    int beg = 0, end = 0;
-    if (valid) { beg = lm_start[l]; end = lm_start[l + 1]; }
-    // (what depends on the landmark alone is asked for with its range, not after the sums below: two trips off the dependent path)
-    const int lc = valid ? l : 0;
-    const double* Li = Linv + (size_t)lc * kLmRec;
-    const double Li0 = Li[0], Li1 = Li[1], Li2 = Li[2], Li3 = Li[3], Li4 = Li[4], Li5 = Li[5];
-    const double* zl = z + (size_t)lc * kLmRec;
-    const double zl0 = zl[0], zl1 = zl[1], zl2 = zl[2];
-    double a0 = 0, a1 = 0, a2 = 0;
-    // (A y_cam of the lane's first two factors stays in registers for the second pass: a track longer than 16 views is rare, and
-    // recomputing it costs the row again plus a three-deep chain of dependent gathers — camera pose id, its tangent offsets, y)
-    double jk0[2] = {0.0, 0.0}, jk1[2] = {0.0, 0.0};
-    int it = 0;
-    // (no C rows — Visual::no_cr: the sums are taken with the B rows, sum_a B_a^T (A_a y), and C^T = Linv B^T is applied to them once per landmark below)
-    const bool no_cr = CR == nullptr;
+    // (y_lds: the same in every workgroup of the launch — the staged form has a barrier of its own)
     const bool compact = ja == kJACompact;
-    for (int f = beg + sub; f < end; f += 8, ++it) {
-      const double2* C2 = no_cr ? reinterpret_cast<const double2*>(JB + (size_t)f * 6) : reinterpret_cast<const double2*>(CR + (size_t)f * 8);
-      const double2 ca = C2[0], cb = C2[1], cc = C2[2];
-      const double C[6] = {ca.x, ca.y, cb.x, cb.y, cc.x, cc.y};
-      const int cp = cam_pose[f];
-      double j0, j1;
-      if (compact) pose_part_compact(J + (size_t)f * kJACompact, C, cp_tq[cp], cp_tp[cp], y_pose, j0, j1);   // (compact implies no C rows: C is the B row)
-      else pose_part(J + (size_t)f * kJAStride, cp_tq[cp], cp_tp[cp], y_pose, j0, j1);
-      if (it == 0) { jk0[0] = j0; jk1[0] = j1; } else if (it == 1) { jk0[1] = j0; jk1[1] = j1; }
-      a0 += C[0] * j0 + C[3] * j1; a1 += C[1] * j0 + C[4] * j1; a2 += C[2] * j0 + C[5] * j1;
-    }
-#pragma unroll
-    for (int o = 4; o > 0; o >>= 1) { a0 += __shfl_xor(a0, o, 8); a1 += __shfl_xor(a1, o, 8); a2 += __shfl_xor(a2, o, 8); }
-    if (no_cr) {   // a <- Linv a   (Linv lower triangular: Li0 | Li1 Li2 | Li3 Li4 Li5)
-      const double b0 = a0, b1 = a1, b2 = a2;
-      a0 = Li0 * b0; a1 = Li1 * b0 + Li2 * b1; a2 = Li3 * b0 + Li4 * b1 + Li5 * b2;
-    }
-    if (valid) {   // (every one of the 8 lanes holds the sums)
-      const double w0 = zl0 - a0, w1 = zl1 - a1, w2 = zl2 - a2;
-      // y = Linv^T w
-      const double y0 = Li0 * w0 + Li1 * w1 + Li3 * w2;
-      const double y1 = Li2 * w1 + Li4 * w2;
-      const double y2 = Li5 * w2;
-      if (sub == 0) {
-        const int to = n_pose + 3 * l;
-        delta[to] = -y0; delta[to + 1] = -y1; delta[to + 2] = -y2;
-        if (up.n_blocks > 0) {   // the landmark's candidate and its terms of the step / x norms
-          const int xo = up.lm_xoff[l];
-          const double x0 = up.x[xo], x1 = up.x[xo + 1], x2v = up.x[xo + 2];
-          const double c0 = x0 + (-y0), c1 = x1 + (-y1), c2 = x2v + (-y2);
-          up.x_cand[xo] = c0; up.x_cand[xo + 1] = c1; up.x_cand[xo + 2] = c2;
-          const double e0 = x0 - c0, e1 = x1 - c1, e2 = x2v - c2;
-          upd_d2 = e0 * e0 + e1 * e1 + e2 * e2; upd_x2 = x0 * x0 + x1 * x1 + x2v * x2v;
-        }
-      }
-      it = 0;
-      for (int f = beg + sub; f < end; f += 8, ++it) {
-        const double2* B2 = reinterpret_cast<const double2*>(JB + (size_t)f * 6);
-        const double2 ba = B2[0], bb = B2[1], bc = B2[2];
-        const double Bf[6] = {ba.x, ba.y, bb.x, bb.y, bc.x, bc.y};
-        double j0, j1;
-        if (it == 0) { j0 = jk0[0]; j1 = jk1[0]; }
-        else if (it == 1) { j0 = jk0[1]; j1 = jk1[1]; }
-        else if (compact) { const int cp = cam_pose[f]; pose_part_compact(J + (size_t)f * kJACompact, Bf, cp_tq[cp], cp_tp[cp], y_pose, j0, j1); }
-        else { const int cp = cam_pose[f]; pose_part(J + (size_t)f * kJAStride, cp_tq[cp], cp_tp[cp], y_pose, j0, j1); }
-        const double d0 = -(j0 + Bf[0] * y0 + Bf[1] * y1 + Bf[2] * y2), d1 = -(j1 + Bf[3] * y0 + Bf[4] * y1 + Bf[5] * y2);
-        const double2 rf = r[f];
-        acc -= d0 * (rf.x + 0.5 * d0) + d1 * (rf.y + 0.5 * d1);
-      }
-    }
+    if (y_lds && compact) backsub_lm_group<true, true>(bsg_bx, n_lm, lm_start, J, JB, r, CR, fac_t, Linv, z, n_pose, y_pose, delta, up, acc, upd_d2, upd_x2);
+    else if (y_lds) backsub_lm_group<true, false>(bsg_bx, n_lm, lm_start, J, JB, r, CR, fac_t, Linv, z, n_pose, y_pose, delta, up, acc, upd_d2, upd_x2);
+    else if (compact) backsub_lm_group<false, true>(bsg_bx, n_lm, lm_start, J, JB, r, CR, fac_t, Linv, z, n_pose, y_pose, delta, up, acc, upd_d2, upd_x2);
+    else backsub_lm_group<false, false>(bsg_bx, n_lm, lm_start, J, JB, r, CR, fac_t, Linv, z, n_pose, y_pose, delta, up, acc, upd_d2, upd_x2);
   } else {
     const int f = n_elim + (bsg_bx - n_lm_groups) * 256 + (int)threadIdx.x;
     if (f < n) {
-      const int cp = cam_pose[f];
-      double j0, j1;
-      pose_part(J + (size_t)f * kJAStride, cp_tq[cp], cp_tp[cp], y_pose, j0, j1);   // (a window with factors of constant landmarks keeps the full layout)
+      const int2 t = fac_t[f];
+      double A[12], j0, j1;
+      const double none[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      pose_row_load<false>(J, f, A);   // (a window with factors of constant landmarks keeps the full layout)
       const double2 rf = r[f];
+      pose_row_dot<false, false>(A, none, t.x, t.y, y_pose, j0, j1);
       acc = -((-j0) * (rf.x - 0.5 * j0) + (-j1) * (rf.y - 0.5 * j1));
     }
   }
@@ -713,8 +816,8 @@ __device__ __forceinline__ void backsub_mcc_kernel_body(const int bsg_bx, const 
     if (threadIdx.x == 0) { up.part[2 * slot] = a; up.part[2 * slot + 1] = c; }
   }
 }
-__global__ __launch_bounds__(256) void backsub_mcc_kernel(int n_lm, int n_lm_groups, int n_elim, int n, const int* __restrict__ lm_start, const double* __restrict__ J, int ja, const double* __restrict__ JB, const double2* __restrict__ r, const double* __restrict__ CR, const int* __restrict__ cam_pose, const int* __restrict__ cp_tq, const int* __restrict__ cp_tp, const double* __restrict__ Linv, const double* __restrict__ z, int n_pose, const double* __restrict__ y_pose, double* __restrict__ delta, double* __restrict__ mcc_part, int n_vis_blocks, SmallGroupSet small, int n_small_units, UpdateRide up, int first_update_block) {
-  backsub_mcc_kernel_body((int)blockIdx.x, (int)gridDim.x, n_lm, n_lm_groups, n_elim, n, lm_start, J, ja, JB, r, CR, cam_pose, cp_tq, cp_tp, Linv, z, n_pose, y_pose, delta, mcc_part, n_vis_blocks, small, n_small_units, up, first_update_block);
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void backsub_mcc_kernel(int n_lm, int n_lm_groups, int n_elim, int n, const int* __restrict__ lm_start, const double* __restrict__ J, int ja, const double* __restrict__ JB, const double2* __restrict__ r, const double* __restrict__ CR, const int2* __restrict__ fac_t, const double* __restrict__ Linv, const double* __restrict__ z, int n_pose, const double* __restrict__ y_pose, int y_lds, double* __restrict__ delta, double* __restrict__ mcc_part, int n_vis_blocks, SmallGroupSet small, int n_small_units, UpdateRide up, int first_update_block) {
+  backsub_mcc_kernel_body((int)blockIdx.x, (int)gridDim.x, n_lm, n_lm_groups, n_elim, n, lm_start, J, ja, JB, r, CR, fac_t, Linv, z, n_pose, y_pose, y_lds, delta, mcc_part, n_vis_blocks, small, n_small_units, up, first_update_block);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
 struct backsub_mcc_kernel_Args {
@@ -729,9 +832,7 @@ struct backsub_mcc_kernel_Args {
   const double* JB;
   const double2* r;
   const double* CR;
-  const int* cam_pose;
-  const int* cp_tq;
-  const int* cp_tp;
+  const int2* fac_t;
   const double* Linv;
   const double* z;
   int n_pose;
@@ -758,9 +859,7 @@ struct backsub_mcc_kernel_ArgsG {
   const double __attribute__((address_space(1)))* JB;
   const double2 __attribute__((address_space(1)))* r;
   const double __attribute__((address_space(1)))* CR;
-  const int __attribute__((address_space(1)))* cam_pose;
-  const int __attribute__((address_space(1)))* cp_tq;
-  const int __attribute__((address_space(1)))* cp_tp;
+  const int2 __attribute__((address_space(1)))* fac_t;
   const double __attribute__((address_space(1)))* Linv;
   const double __attribute__((address_space(1)))* z;
   int n_pose;
@@ -775,11 +874,11 @@ struct backsub_mcc_kernel_ArgsG {
 };
 static_assert(sizeof(backsub_mcc_kernel_ArgsG) == sizeof(backsub_mcc_kernel_Args), "layout");
 
-__global__ __launch_bounds__(256) void backsub_mcc_kernel_batch(const backsub_mcc_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void backsub_mcc_kernel_batch(const backsub_mcc_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list, int bsg_y_lds) {
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.y];
   const backsub_mcc_kernel_ArgsG& a = reinterpret_cast<const backsub_mcc_kernel_ArgsG*>(bsg_A)[bsg_w];
   if ((int)blockIdx.x >= a.bsg_grid) return;
-  backsub_mcc_kernel_body((int)blockIdx.x, a.bsg_grid, a.n_lm, a.n_lm_groups, a.n_elim, a.n, (const int*)a.lm_start, (const double*)a.J, a.ja, (const double*)a.JB, (const double2*)a.r, (double*)a.CR, (const int*)a.cam_pose, (const int*)a.cp_tq, (const int*)a.cp_tp, (const double*)a.Linv, (const double*)a.z, a.n_pose, (const double*)a.y_pose, (double*)a.delta, (double*)a.mcc_part, a.n_vis_blocks, a.small, a.n_small_units, a.up, a.first_update_block);
+  backsub_mcc_kernel_body((int)blockIdx.x, a.bsg_grid, a.n_lm, a.n_lm_groups, a.n_elim, a.n, (const int*)a.lm_start, (const double*)a.J, a.ja, (const double*)a.JB, (const double2*)a.r, (double*)a.CR, (const int2*)a.fac_t, (const double*)a.Linv, (const double*)a.z, a.n_pose, (const double*)a.y_pose, bsg_y_lds, (double*)a.delta, (double*)a.mcc_part, a.n_vis_blocks, a.small, a.n_small_units, a.up, a.first_update_block);
 }
 
 // ---- the same launches over several windows (bsgpu_batch.cpp): one table entry per window, grids as the lone launches compute them
@@ -826,21 +925,27 @@ void batchargs_backsub_mcc(BatchArgTable& t, const Visual& v, int n_pose, const 
   const int extra = small ? (n_small_units + 1) / 2 : 0;
   const int upd_units = (upd && upd->n_blocks > 0) ? (upd->n_blocks + 255) / 256 : 0;
   a.bsg_grid = grid > 0 ? grid + extra + upd_units : 0;
-  a.n_lm = v.n_lm; a.n_lm_groups = g_lm; a.n_elim = v.n_elim; a.n = v.n; a.lm_start = v.lm_start; a.J = v.J; a.ja = v.ja; a.JB = v.JB; a.r = v.r; a.CR = v.no_cr ? nullptr : v.CR; a.cam_pose = v.cam_pose;
-  a.cp_tq = v.cp_tq; a.cp_tp = v.cp_tp; a.Linv = v.Linv; a.z = v.z; a.n_pose = n_pose; a.y_pose = y_pose; a.delta = delta; a.mcc_part = mcc_part; a.n_vis_blocks = grid;
+  a.n_lm = v.n_lm; a.n_lm_groups = g_lm; a.n_elim = v.n_elim; a.n = v.n; a.lm_start = v.lm_start; a.J = v.J; a.ja = v.ja; a.JB = v.JB; a.r = v.r; a.CR = v.no_cr ? nullptr : v.CR; a.fac_t = v.fac_t;
+  a.Linv = v.Linv; a.z = v.z; a.n_pose = n_pose; a.y_pose = y_pose; a.delta = delta; a.mcc_part = mcc_part; a.n_vis_blocks = grid;
   a.small = small ? *small : SmallGroupSet(); a.n_small_units = small ? n_small_units : 0; a.up = upd_units ? *upd : UpdateRide(); a.first_update_block = grid + extra;
   t.push(a);
+  // (y_cam staged in LDS: one decision for the launch, from its largest window)
+  if (a.bsg_grid > 0 && g_lm > 0) {
+    const size_t lds = backsub_stage_bytes(n_pose);
+    if (lds == 0) t.lds_over = true; else t.lds = std::max(t.lds, lds);
+  }
 }
 void launch_backsub_mcc_batch(hipStream_t s, const BatchArgTable& t, const BatchDyn* dyn, int list, int n) {
   if (n <= 0 || t.max_grid <= 0) return;
-  hipLaunchKernelGGL(backsub_mcc_kernel_batch, dim3(t.max_grid, n), dim3(256), 0, s, static_cast<const backsub_mcc_kernel_Args*>(t.dev), dyn, list);
+  const size_t lds = t.lds_over ? 0 : t.lds;
+  hipLaunchKernelGGL(backsub_mcc_kernel_batch, dim3(t.max_grid, n), dim3(256), lds, s, static_cast<const backsub_mcc_kernel_Args*>(t.dev), dyn, list, lds > 0 ? 1 : 0);
 }
 int backsub_mcc_groups(const Visual& v) { return (v.n_lm * 8 + 255) / 256 + (v.n - v.n_elim + 255) / 256; }
 // ... with the model-cost terms of the window's dense prior (marg_body.h; they read the pose step only: the landmarks a prior names are not
 // eliminated) as the launch's last workgroups, four rows each, instead of marg_mcc_kernel behind it (4.6 us)
-__global__ __launch_bounds__(256) void backsub_mcc_marg_kernel(int n_lm, int n_lm_groups, int n_elim, int n, const int* __restrict__ lm_start, const double* __restrict__ J, int ja, const double* __restrict__ JB, const double2* __restrict__ r, const double* __restrict__ CR, const int* __restrict__ cam_pose, const int* __restrict__ cp_tq, const int* __restrict__ cp_tp, const double* __restrict__ Linv, const double* __restrict__ z, int n_pose, const double* __restrict__ y_pose, double* __restrict__ delta, double* __restrict__ mcc_part, int n_vis_blocks, SmallGroupSet small, int n_small_units, UpdateRide up, int first_update_block, MargDev m, double* __restrict__ marg_part, int first_marg_block) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void backsub_mcc_marg_kernel(int n_lm, int n_lm_groups, int n_elim, int n, const int* __restrict__ lm_start, const double* __restrict__ J, int ja, const double* __restrict__ JB, const double2* __restrict__ r, const double* __restrict__ CR, const int2* __restrict__ fac_t, const double* __restrict__ Linv, const double* __restrict__ z, int n_pose, const double* __restrict__ y_pose, int y_lds, double* __restrict__ delta, double* __restrict__ mcc_part, int n_vis_blocks, SmallGroupSet small, int n_small_units, UpdateRide up, int first_update_block, MargDev m, double* __restrict__ marg_part, int first_marg_block) {
   if ((int)blockIdx.x >= first_marg_block) { marg_mcc_kernel_body(4 * ((int)blockIdx.x - first_marg_block), m, delta, marg_part); return; }
-  backsub_mcc_kernel_body((int)blockIdx.x, first_marg_block, n_lm, n_lm_groups, n_elim, n, lm_start, J, ja, JB, r, CR, cam_pose, cp_tq, cp_tp, Linv, z, n_pose, y_pose, delta, mcc_part, n_vis_blocks, small, n_small_units, up, first_update_block);
+  backsub_mcc_kernel_body((int)blockIdx.x, first_marg_block, n_lm, n_lm_groups, n_elim, n, lm_start, J, ja, JB, r, CR, fac_t, Linv, z, n_pose, y_pose, y_lds, delta, mcc_part, n_vis_blocks, small, n_small_units, up, first_update_block);
 }
 bool launch_backsub_mcc(hipStream_t s, const Visual& v, int n_pose, const double* y_pose, double* delta, double* mcc_part,
                         const SmallGroupSet* small, int n_small_units, const UpdateRide* upd, const MargDev* marg, double* marg_part) {
@@ -848,17 +953,29 @@ bool launch_backsub_mcc(hipStream_t s, const Visual& v, int n_pose, const double
   if (grid == 0) return false;
   const int extra = small ? (n_small_units + 1) / 2 : 0;
   const int upd_units = (upd && upd->n_blocks > 0) ? (upd->n_blocks + 255) / 256 : 0;
+  const size_t lds = g_lm > 0 ? backsub_stage_bytes(n_pose) : 0;
   if (marg && marg_part && marg->rows > 0) {
     const int own = grid + extra + upd_units;
-    hipLaunchKernelGGL(backsub_mcc_marg_kernel, dim3(own + (marg->rows + 3) / 4), dim3(256), 0, s, v.n_lm, g_lm, v.n_elim, v.n, v.lm_start, v.J, v.ja, v.JB, v.r, v.no_cr ? nullptr : v.CR, v.cam_pose,
-                       v.cp_tq, v.cp_tp, v.Linv, v.z, n_pose, y_pose, delta, mcc_part, grid, small ? *small : SmallGroupSet(), small ? n_small_units : 0,
+    hipLaunchKernelGGL(backsub_mcc_marg_kernel, dim3(own + (marg->rows + 3) / 4), dim3(256), lds, s, v.n_lm, g_lm, v.n_elim, v.n, v.lm_start, v.J, v.ja, v.JB, v.r, v.no_cr ? nullptr : v.CR, v.fac_t,
+                       v.Linv, v.z, n_pose, y_pose, lds > 0 ? 1 : 0, delta, mcc_part, grid, small ? *small : SmallGroupSet(), small ? n_small_units : 0,
                        upd_units ? *upd : UpdateRide(), grid + extra, *marg, marg_part, own);
     return true;
   }
-  hipLaunchKernelGGL(backsub_mcc_kernel, dim3(grid + extra + upd_units), dim3(256), 0, s, v.n_lm, g_lm, v.n_elim, v.n, v.lm_start, v.J, v.ja, v.JB, v.r, v.no_cr ? nullptr : v.CR, v.cam_pose,
-                     v.cp_tq, v.cp_tp, v.Linv, v.z, n_pose, y_pose, delta, mcc_part, grid, small ? *small : SmallGroupSet(), small ? n_small_units : 0,
+  hipLaunchKernelGGL(backsub_mcc_kernel, dim3(grid + extra + upd_units), dim3(256), lds, s, v.n_lm, g_lm, v.n_elim, v.n, v.lm_start, v.J, v.ja, v.JB, v.r, v.no_cr ? nullptr : v.CR, v.fac_t,
+                     v.Linv, v.z, n_pose, y_pose, lds > 0 ? 1 : 0, delta, mcc_part, grid, small ? *small : SmallGroupSet(), small ? n_small_units : 0,
                      upd_units ? *upd : UpdateRide(), grid + extra);
   return false;
+}
+
+// Visual::fac_t from the two tables it joins — once per finalize(), behind whichever flattening (host upload or device kernels, both queued on s) built them
+__global__ void fac_t_kernel(int n, const int* __restrict__ cam_pose, const int* __restrict__ cp_tq, const int* __restrict__ cp_tp, int2* __restrict__ fac_t) {
+  const int f = blockIdx.x * 256 + threadIdx.x;
+  if (f >= n) return;
+  const int cp = cam_pose[f];
+  fac_t[f] = make_int2(cp_tq[cp], cp_tp[cp]);
+}
+void launch_fac_t(hipStream_t s, const Visual& v) {
+  if (v.n > 0) hipLaunchKernelGGL(fac_t_kernel, dim3((v.n + 255) / 256), dim3(256), 0, s, v.n, v.cam_pose, v.cp_tq, v.cp_tp, v.fac_t);
 }
 
 }  // namespace bsg

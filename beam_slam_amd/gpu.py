@@ -160,6 +160,16 @@ class GpuSolver(capi.Solver):
         self._chk(fn(self._ctx, out.ctypes.data))
         return out
 
+    def backsub_tangent_table(self, n):
+        """bsgpu_backsub_tangent_table for the n reprojection factors -> (fac_t (n,2), the same joined from the per-camera-pose tables (n,2));
+        -2 where a factor is not in the landmark tables."""
+        import numpy as np
+        ft, jn = np.full((n, 2), -2, np.int32), np.full((n, 2), -2, np.int32)
+        fn = lib().bsgpu_backsub_tangent_table
+        fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        self._chk(fn(self._ctx, ft.ctypes.data, jn.ctypes.data))
+        return ft, jn
+
     def triangulate(self, track_start, q_block, p_block, pixels, camera=0, truncate_pixels=True, max_dist=-1.0, max_reproj=-1.0):
         """bsgpu_triangulate: DLT triangulation of a batch of feature tracks at the current values -> (points (n,3), status (n,))."""
         import numpy as np

@@ -469,6 +469,12 @@ int bsgpu_covariance_requests(bsgpu_ctx* ctx, int32_t n_requests, const int32_t*
  * camera.  err: bsgpu_nfactors-sized, i.e. n(REPROJ) + n(REPROJ_ONLINE_CALIB) doubles.                          */
 int bsgpu_reprojection_errors(bsgpu_ctx* ctx, double* err);
 
+/* Test hook: the tangent offsets (q block, p block; -1 = constant) the landmark back-substitution reads per reprojection factor
+ * (fac_t), and the same pair joined from the two tables it is built from (camera-pose id per factor, offsets per camera pose).
+ * Both 2 x (n(REPROJ) + n(REPROJ_ONLINE_CALIB)) int32, insertion order as bsgpu_reprojection_errors; the entries of factors that are
+ * not in the landmark tables (a landmark shared with another kind of factor) are left as the caller set them.                      */
+int bsgpu_backsub_tangent_table(bsgpu_ctx* ctx, int32_t* fac_t, int32_t* joined);
+
 /* bs_common::PreIntegrator::Integrate (bs_common/src/bs_common/preintegrator.cpp:26-143) for a batch of keyframe
  * intervals on the device: interval i integrates samples [sample_start[i], sample_start[i+1]) (time-ordered,
  * t / gyro w[3] / accel a[3] per sample) up to t_end[i] with the bias estimates bg[3i..], ba[3i..], and the
