@@ -116,6 +116,7 @@ SYMBOLS = [
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
     "covariance_requests", "localize_frames", "num_factorizations", "essential_ransac", "absolute_pose_ransac",
     "relative_pose_ransac", "inertial_alignment", "register_scans", "register_scans_error", "backsub_tangent_table",
+    "scan_context_describe", "scan_context_match", "scan_context_error",
 ]
 
 _dp = C.POINTER(C.c_double)
@@ -146,6 +147,12 @@ ICP_MAX_CELLS, ICP_MAX_ITER = 1 << 22, 1000
 ICP_DEFAULTS = dict(max_corr=1.0, max_iter=50, t_eps=1e-8, fit_eps=1e-2, rotation_threshold=0.99999, rel_mse_eps=1e-5)
 REGISTER_SCANS_ARGTYPES = [C.c_int, C.c_int32, _ip, _dp, _ip, _dp, _dp, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double,
                            C.c_double, _dp, _dp, _dp, _ip, _ip, _ip]
+#: bsgpu_scan_context_describe / bsgpu_scan_context_match: the descriptor's shape, the limits, the reference's shipped parameters
+#: (SCManager's LIDAR_HEIGHT, PC_MAX_RADIUS, NUM_CANDIDATES_FROM_TREE, SEARCH_RATIO, SC_DIST_THRES, recalled) and the typed prototypes
+SC_RINGS, SC_SECTORS, SC_MAX_CANDIDATES, SC_MAX_TREE_CANDIDATES, SC_MAX_SCAN_POINTS = 20, 60, 65536, 64, 65535 * 4096
+SC_DEFAULTS = dict(lidar_height=2.0, max_radius=80.0, n_tree_candidates=10, search_ratio=0.1, dist_thres=0.3)
+SCAN_CONTEXT_DESCRIBE_ARGTYPES = [C.c_int, C.c_int32, _ip, _dp, C.c_int32, _ip, _ip, _dp, C.c_double, C.c_double, _dp, _dp, _dp, _ip]
+SCAN_CONTEXT_MATCH_ARGTYPES = [C.c_int, C.c_int32, _ip, _dp, _ip, _dp, C.c_int32, C.c_double, C.c_double, _ip, _dp, _ip, _dp, _dp, _ip]
 
 
 def _ptr(a, typ):

@@ -1,5 +1,5 @@
 // The front-end entry points of the C-ABI (include/bsgpu.h): bsgpu_preintegrate, bsgpu_inertial_alignment, bsgpu_register_scans,
-// bsgpu_triangulate, bsgpu_localize_frames and the three RANSACs.  Each checks its arguments, describes its arrays as a StageLayout (staging.h:
+// bsgpu_scan_context_describe, bsgpu_scan_context_match, bsgpu_triangulate, bsgpu_localize_frames and the three RANSACs.  Each checks its arguments, describes its arrays as a StageLayout (staging.h:
 // [inputs | outputs | scratch] in one device allocation), runs one kernel between one copy in and one copy out, and hands the
 // results to the caller's arrays: nothing is written to them unless the call succeeds.
 #include <algorithm>
@@ -9,12 +9,14 @@
 #include "bsgpu_ctx.h"
 #include "icp.h"
 #include "inertial_align.h"
+#include "scan_context.h"
 #include "staging.h"
 
 using namespace bsg;
 
 namespace {
 thread_local std::string g_register_scans_error;   // what this thread's last failed bsgpu_register_scans objected to (it has no context to keep it)
+thread_local std::string g_scan_context_error;     // the same for bsgpu_scan_context_describe and bsgpu_scan_context_match
 }
 
 extern "C" {
@@ -188,6 +190,149 @@ int bsgpu_register_scans(int device, int32_t n_pairs, const int32_t* ref_start, 
   return BSGPU_OK;
 } catch (...) {
   try { g_register_scans_error = "register_scans: out of host memory"; } catch (...) {}
+  return api_exception(nullptr);
+}
+
+const char* bsgpu_scan_context_error(void) { return g_scan_context_error.c_str(); }
+
+int bsgpu_scan_context_describe(int device, int32_t n_scans, const int32_t* scan_start, const double* points, int32_t n_aggregates,
+                                const int32_t* member_start, const int32_t* member_scan, const double* member_T, double lidar_height,
+                                double max_radius, double* desc, double* ring_key, double* sector_key, int32_t* n_binned) try {
+  const auto refuse = [](int code, const char* why) { g_scan_context_error = why; return code; };
+  if (n_scans < 0 || n_aggregates < 0 || !scan_start || !member_start || !desc) return refuse(BSGPU_ERR_INVALID, "scan_context_describe: null argument");
+  if (!(max_radius > 0.0) || !std::isfinite(max_radius)) return refuse(BSGPU_ERR_INVALID, "scan_context_describe: max_radius must be positive and finite");
+  if (!std::isfinite(lidar_height)) return refuse(BSGPU_ERR_INVALID, "scan_context_describe: lidar_height must be finite");
+  const auto finite_scan = [&](int k) {
+    if (scan_start[k + 1] > scan_start[k] && !points) return false;
+    for (size_t i = 3 * (size_t)scan_start[k]; i < 3 * (size_t)scan_start[k + 1]; ++i) if (!std::isfinite(points[i])) return false;
+    return true;
+  };
+  switch (check_start_table(scan_start, n_scans, kScMaxScanPoints)) {     // (the table alone first: a scan too long is refused before a point is read)
+    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "scan_context_describe: scan_start[0] must be 0");
+    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "scan_context_describe: scan_start must be non-decreasing");
+    case kStartTooLong: return refuse(BSGPU_ERR_UNSUPPORTED, "scan_context_describe: a scan holds more than BSGPU_SC_MAX_SCAN_POINTS points");
+    default: break;
+  }
+  if (check_start_table(scan_start, n_scans, INT_MAX, finite_scan) != kStartOk)
+    return refuse(BSGPU_ERR_INVALID, "scan_context_describe: null or non-finite points");
+  const auto members_ok = [&](int a) {
+    if (member_start[a + 1] > member_start[a] && !member_scan) return false;
+    for (int m = member_start[a]; m < member_start[a + 1]; ++m) if (member_scan[m] < 0 || member_scan[m] >= n_scans) return false;
+    return true;
+  };
+  switch (check_start_table(member_start, n_aggregates, INT_MAX, members_ok)) {
+    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "scan_context_describe: member_start[0] must be 0");
+    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "scan_context_describe: member_start must be non-decreasing");
+    case kStartBadItem: return refuse(BSGPU_ERR_INVALID, "scan_context_describe: null member_scan or a member index out of range");
+    default: break;
+  }
+  if (n_aggregates == 0) return BSGPU_OK;
+  const size_t na = (size_t)n_aggregates, nm = (size_t)member_start[n_aggregates], np = (size_t)scan_start[n_scans];
+  static const double eye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  std::vector<double> T(12 * nm);
+  for (size_t i = 0; i < T.size(); ++i) {
+    T[i] = member_T ? member_T[i] : eye[i % 12];
+    if (!std::isfinite(T[i])) return refuse(BSGPU_ERR_INVALID, "scan_context_describe: non-finite member_T");
+  }
+  std::vector<int32_t> member_agg(nm);
+  int max_chunks = 0;
+  for (int a = 0; a < n_aggregates; ++a)
+    for (int m = member_start[a]; m < member_start[a + 1]; ++m) {
+      member_agg[m] = a;
+      const int n = scan_start[member_scan[m] + 1] - scan_start[member_scan[m]];
+      max_chunks = std::max(max_chunks, (int)(((int64_t)n + kScChunk - 1) / kScChunk));
+    }
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "scan_context_describe: hipSetDevice failed"); }
+  StageLayout L;
+  const int s_ss = L.in(scan_start, 4 * ((size_t)n_scans + 1)), s_pts = L.in(points, 24 * np), s_ms = L.in(member_scan, 4 * nm),
+            s_ma = L.in(member_agg.data(), 4 * nm), s_T = L.in(T.data(), 96 * nm);
+  const int s_desc = L.out(desc, 8 * kScBins * na), s_rk = L.out(ring_key, 8 * kScRings * na), s_sk = L.out(sector_key, 8 * kScSectors * na),
+            s_nb = L.out(n_binned, 4 * na);
+  // the kernels' working arrays (the launch clears them): every aggregate's table of integer keys, its count of kept points
+  const int s_tab = L.scratch(8 * kScBins * na), s_cnt = L.scratch(4 * na);
+  DeviceStage D(L);
+  if (!D) return refuse(BSGPU_ERR_DEVICE, "scan_context_describe: out of device memory");
+  const auto F = [&](int s) { return D.ptr<double>(s); };
+  const auto I = [&](int s) { return D.ptr<int>(s); };
+  const hipError_t e = D.run(nullptr, [&] {
+    launch_scan_context_describe(nullptr, n_aggregates, (int)nm, max_chunks, I(s_ss), F(s_pts), I(s_ms), I(s_ma), F(s_T), lidar_height, max_radius,
+                                 F(s_desc), F(s_rk), F(s_sk), I(s_nb), D.ptr<unsigned long long>(s_tab), I(s_cnt));
+  });
+  if (e != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "scan_context_describe: device error"); }
+  L.scatter();
+  return BSGPU_OK;
+} catch (...) {
+  try { g_scan_context_error = "scan_context_describe: out of host memory"; } catch (...) {}
+  return api_exception(nullptr);
+}
+
+int bsgpu_scan_context_match(int device, int32_t n_sets, const int32_t* query_start, const double* query_desc, const int32_t* cand_start,
+                             const double* cand_desc, int32_t n_tree_candidates, double search_ratio, double dist_thres, int32_t* best_cand,
+                             double* best_dist, int32_t* best_shift, double* yaw, double* dist_all, int32_t* shift_all) try {
+  const auto refuse = [](int code, const char* why) { g_scan_context_error = why; return code; };
+  if (n_sets < 0 || !query_start || !cand_start || !best_cand || !best_dist || !best_shift)
+    return refuse(BSGPU_ERR_INVALID, "scan_context_match: null argument");
+  if (!(search_ratio >= 0.0)) return refuse(BSGPU_ERR_INVALID, "scan_context_match: search_ratio must not be negative or NaN");
+  if (!(dist_thres >= 0.0)) return refuse(BSGPU_ERR_INVALID, "scan_context_match: dist_thres must not be negative or NaN");
+  const auto finite_items = [](const int32_t* start, const double* d) {
+    return [start, d](int k) {
+      if (start[k + 1] > start[k] && !d) return false;
+      for (size_t i = (size_t)kScBins * start[k]; i < (size_t)kScBins * start[k + 1]; ++i) if (!std::isfinite(d[i])) return false;
+      return true;
+    };
+  };
+  switch (check_start_table(query_start, n_sets, INT_MAX, finite_items(query_start, query_desc))) {
+    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "scan_context_match: query_start[0] must be 0");
+    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "scan_context_match: query_start must be non-decreasing");
+    case kStartBadItem: return refuse(BSGPU_ERR_INVALID, "scan_context_match: null or non-finite query descriptors");
+    default: break;
+  }
+  switch (check_start_table(cand_start, n_sets, kScMaxCandidates)) {     // (the table alone first: a set too long is refused before a descriptor is read)
+    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "scan_context_match: cand_start[0] must be 0");
+    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "scan_context_match: cand_start must be non-decreasing");
+    case kStartTooLong: return refuse(BSGPU_ERR_UNSUPPORTED, "scan_context_match: a set holds more than BSGPU_SC_MAX_CANDIDATES candidates");
+    default: break;
+  }
+  if (check_start_table(cand_start, n_sets, INT_MAX, finite_items(cand_start, cand_desc)) != kStartOk)
+    return refuse(BSGPU_ERR_INVALID, "scan_context_match: null or non-finite candidate descriptors");
+  if (n_tree_candidates > kScMaxTree) return refuse(BSGPU_ERR_UNSUPPORTED, "scan_context_match: n_tree_candidates exceeds BSGPU_SC_MAX_TREE_CANDIDATES");
+  const size_t nq = n_sets > 0 ? (size_t)query_start[n_sets] : 0;
+  if (nq == 0) return BSGPU_OK;
+  const size_t ncand = (size_t)cand_start[n_sets];
+  const int K = n_tree_candidates > 0 ? n_tree_candidates : 0;
+  std::vector<int32_t> query_set(nq);
+  std::vector<int64_t> pair_start(nq);
+  int64_t pairs = 0;
+  int max_cands = 0;
+  bool any_select = false;
+  for (int s = 0; s < n_sets; ++s) {
+    const int nc = cand_start[s + 1] - cand_start[s];
+    if (query_start[s + 1] > query_start[s]) { max_cands = std::max(max_cands, nc); any_select = any_select || (K > 0 && K < nc); }
+    for (int q = query_start[s]; q < query_start[s + 1]; ++q) { query_set[q] = s; pair_start[q] = pairs; pairs += nc; }
+  }
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "scan_context_match: hipSetDevice failed"); }
+  const size_t n_pairs = (size_t)pairs;
+  StageLayout L;
+  const int s_qs = L.in(query_set.data(), 4 * nq), s_ps = L.in(pair_start.data(), 8 * nq), s_qd = L.in(query_desc, 8 * kScBins * nq),
+            s_cs = L.in(cand_start, 4 * ((size_t)n_sets + 1)), s_cd = L.in(cand_desc, 8 * kScBins * ncand);
+  const int s_bc = L.out(best_cand, 4 * nq), s_bd = L.out(best_dist, 8 * nq), s_bs = L.out(best_shift, 4 * nq), s_yaw = L.out(yaw, 8 * nq),
+            s_da = L.out(dist_all, 8 * n_pairs), s_sa = L.out(shift_all, 4 * n_pairs);
+  // the pre-selection's working arrays (written before they are read, and only for sets larger than K): ring-key distances, flags
+  const int s_d2 = L.scratch(any_select ? 8 * n_pairs : 0), s_take = L.scratch(any_select ? 4 * n_pairs : 0);
+  DeviceStage D(L);
+  if (!D) return refuse(BSGPU_ERR_DEVICE, "scan_context_match: out of device memory");
+  const auto F = [&](int s) { return D.ptr<double>(s); };
+  const auto I = [&](int s) { return D.ptr<int>(s); };
+  const hipError_t e = D.run(nullptr, [&] {
+    launch_scan_context_match(nullptr, (int)nq, max_cands, any_select, I(s_qs), D.ptr<long long>(s_ps), F(s_qd), I(s_cs), F(s_cd), K,
+                              sc_search_radius(search_ratio), dist_thres, I(s_bc), F(s_bd), I(s_bs), F(s_yaw), F(s_da), I(s_sa), F(s_d2),
+                              I(s_take));
+  });
+  if (e != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "scan_context_match: device error"); }
+  L.scatter();
+  return BSGPU_OK;
+} catch (...) {
+  try { g_scan_context_error = "scan_context_match: out of host memory"; } catch (...) {}
   return api_exception(nullptr);
 }
 

@@ -561,6 +561,18 @@ void launch_register_scans(hipStream_t s, int n_pairs, int max_targets, int n_ta
                            const IcpGrid* grids, double max_corr, const IcpParams& P, double* T, double* T_ref_tgt, double* mse, int* n_corr,
                            int* n_iters, int* status, double* tq, int* tcell, int* cells, int* tile_sum, double* rec, double* part,
                            double* mse_prev, int* done);
+// Scan Context place recognition (k_scan_context.hip, bsgpu_scan_context_describe / _match).  Inputs as the C-ABI's, on the device, plus
+// what the host derives: member_agg (a member's aggregate), max_chunks (chunks of kScChunk points of the longest scan a member names),
+// query_set (a query's set), pair_start (n_queries: where a query's (query, candidate) entries begin), R (the refinement radius).
+// Scratch: table kScBins keys / count 1 per aggregate; d2 / take 1 per (query, candidate) entry.  Every output is written.
+void launch_scan_context_describe(hipStream_t s, int n_aggregates, int n_members, int max_chunks, const int* scan_start, const double* points,
+                                  const int* member_scan, const int* member_agg, const double* member_T, double lidar_height,
+                                  double max_radius, double* desc, double* ring_key, double* sector_key, int* n_binned,
+                                  unsigned long long* table, int* count);
+void launch_scan_context_match(hipStream_t s, int n_queries, int max_cands, bool any_select, const int* query_set, const long long* pair_start,
+                               const double* query_desc, const int* cand_start, const double* cand_desc, int K, int R, double dist_thres,
+                               int* best_cand, double* best_dist, int* best_shift, double* yaw, double* dist_all, int* shift_all, double* d2,
+                               int* take);
 void launch_triangulate(hipStream_t s, int n_tracks, const int* track_start, const int2* pose_off, const double2* pix, const double* x,
                         const DevCamera& cam, bool truncate, double max_dist, double max_reproj, double* points, int* status);
 // frame localisation (k_loc.hip, bsgpu_localize_frames): one workgroup per frame; pts (3 per observation) or pt_off (offset of the

@@ -145,6 +145,81 @@ def register_scans_error():
     return fn().decode()
 
 
+def scan_context_describe(scan_start, points, member_start, member_scan, member_T=None, lidar_height=capi.SC_DEFAULTS["lidar_height"],
+                          max_radius=capi.SC_DEFAULTS["max_radius"], device=0):
+    """bsgpu_scan_context_describe: the Scan Context descriptor of a batch of aggregated scans.  Scan k is
+    points[scan_start[k]:scan_start[k+1]] (lidar frame); aggregate a is the union of its members member_start[a] .. member_start[a+1],
+    member m being scan member_scan[m] through member_T[m] (3 x 4; None: identity).  Returns a dict of arrays: desc (A x 20 x 60),
+    ring_key (A x 20), sector_key (A x 60), n_binned (A)."""
+    import numpy as np
+    ss = np.ascontiguousarray(scan_start, np.int32).reshape(-1)
+    ms = np.ascontiguousarray(member_start, np.int32).reshape(-1)
+    pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    mscan = np.ascontiguousarray(member_scan, np.int32).reshape(-1)
+    mT = None if member_T is None else np.ascontiguousarray(member_T, np.float64).reshape(-1, 3, 4)
+    S, A = ss.size - 1, ms.size - 1
+    if S < 0 or A < 0 or (mT is not None and mT.shape[0] != mscan.size):
+        raise capi.SolverError(capi.ERR_INVALID, "scan_context_describe: array sizes do not agree")
+    if int(ss.max()) > pts.shape[0] or int(ms.max()) > mscan.size:
+        raise capi.SolverError(capi.ERR_INVALID, "scan_context_describe: scan_start / member_start name more entries than were passed")
+    out = dict(desc=np.zeros((A, capi.SC_RINGS, capi.SC_SECTORS)), ring_key=np.zeros((A, capi.SC_RINGS)),
+               sector_key=np.zeros((A, capi.SC_SECTORS)), n_binned=np.zeros(A, np.int32))
+    fn = lib().bsgpu_scan_context_describe
+    fn.argtypes = capi.SCAN_CONTEXT_DESCRIBE_ARGTYPES
+    _dp, _ip = capi._dp, capi._ip
+    d = lambda x: None if x is None else x.ctypes.data_as(_dp)
+    i = lambda x: x.ctypes.data_as(_ip)
+    rc = fn(device, S, i(ss), d(pts), A, i(ms), i(mscan), d(mT), float(lidar_height), float(max_radius), d(out["desc"]), d(out["ring_key"]),
+            d(out["sector_key"]), i(out["n_binned"]))
+    if rc != 0:
+        raise capi.SolverError(rc, scan_context_error())
+    return out
+
+
+def scan_context_match(query_start, query_desc, cand_start, cand_desc, n_tree_candidates=capi.SC_DEFAULTS["n_tree_candidates"],
+                       search_ratio=capi.SC_DEFAULTS["search_ratio"], dist_thres=capi.SC_DEFAULTS["dist_thres"], device=0):
+    """bsgpu_scan_context_match: for every query descriptor the best candidate descriptor of its set over column shifts.  Set s holds
+    queries query_start[s] .. query_start[s+1] and candidates cand_start[s] .. cand_start[s+1].  Returns a dict of arrays: best_cand
+    (index inside the set, -1: none below dist_thres), best_dist, best_shift, yaw (per query); dist_all, shift_all (per query and
+    candidate of its set, in order), pair_start (Q + 1: where a query's entries begin in them)."""
+    import numpy as np
+    qs = np.ascontiguousarray(query_start, np.int32).reshape(-1)
+    cs = np.ascontiguousarray(cand_start, np.int32).reshape(-1)
+    qd = np.ascontiguousarray(query_desc, np.float64).reshape(-1, capi.SC_RINGS, capi.SC_SECTORS)
+    cd = np.ascontiguousarray(cand_desc, np.float64).reshape(-1, capi.SC_RINGS, capi.SC_SECTORS)
+    n_sets = qs.size - 1
+    if n_sets < 0 or cs.size != qs.size:
+        raise capi.SolverError(capi.ERR_INVALID, "scan_context_match: array sizes do not agree")
+    if int(qs.max()) > qd.shape[0] or int(cs.max()) > cd.shape[0]:
+        raise capi.SolverError(capi.ERR_INVALID, "scan_context_match: query_start / cand_start name more descriptors than were passed")
+    Q = max(int(qs[-1]), 0)
+    per_query = np.zeros(Q, np.int64)
+    if (np.diff(qs) >= 0).all() and (np.diff(cs) >= 0).all() and qs[0] == 0 and cs[0] == 0:
+        per_query = np.repeat(np.diff(cs).astype(np.int64), np.diff(qs))
+    pair_start = np.concatenate([[0], np.cumsum(per_query)]).astype(np.int64)
+    P = int(pair_start[-1])
+    out = dict(best_cand=np.zeros(Q, np.int32), best_dist=np.zeros(Q), best_shift=np.zeros(Q, np.int32), yaw=np.zeros(Q),
+               dist_all=np.zeros(P), shift_all=np.zeros(P, np.int32), pair_start=pair_start)
+    fn = lib().bsgpu_scan_context_match
+    fn.argtypes = capi.SCAN_CONTEXT_MATCH_ARGTYPES
+    _dp, _ip = capi._dp, capi._ip
+    d = lambda x: x.ctypes.data_as(_dp)
+    i = lambda x: x.ctypes.data_as(_ip)
+    rc = fn(device, n_sets, i(qs), d(qd), i(cs), d(cd), int(n_tree_candidates), float(search_ratio), float(dist_thres), i(out["best_cand"]),
+            d(out["best_dist"]), i(out["best_shift"]), d(out["yaw"]), d(out["dist_all"]), i(out["shift_all"]))
+    if rc != 0:
+        raise capi.SolverError(rc, scan_context_error())
+    return out
+
+
+def scan_context_error():
+    """What this thread's last failed bsgpu_scan_context_describe or bsgpu_scan_context_match objected to."""
+    fn = lib().bsgpu_scan_context_error
+    fn.restype = ctypes.c_char_p
+    fn.argtypes = []
+    return fn().decode()
+
+
 class GpuSolver(capi.Solver):
     """One bsgpu context on HIP device `device`."""
 

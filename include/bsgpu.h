@@ -577,6 +577,66 @@ int bsgpu_register_scans(int device, int32_t n_pairs, const int32_t* ref_start, 
                          double* mse, int32_t* n_corr, int32_t* n_iters, int32_t* status);
 const char* bsgpu_register_scans_error(void);
 
+/* Scan Context place recognition — the descriptors and the search of RelocCandidateSearchScanContext::FindRelocCandidates
+ * (bs_models/src/lib/reloc/reloc_candidate_search_scan_context.cpp:117-150): the step that decides which scan pairs
+ * AlignSubmapsFromScanMatches (:210-262) hands to the matcher (bsgpu_register_scans).  Two stateless calls, so that a caller can keep
+ * descriptors per keyframe as SCManager does.  [EXT] SCManager is libbeam's copy of the published Scan Context code (Kim & Kim, IROS
+ * 2018) and is not in the reference checkout: everything below is RECALLED, not verified, and it is computed in FP64 where the
+ * original bins float points.  BSGPU_SC_RINGS and BSGPU_SC_SECTORS are compile-time constants (the original's PC_NUM_RING, PC_NUM_SECTOR).
+ *
+ * bsgpu_scan_context_describe (makeScancontext, makeRingkeyFromScancontext, makeSectorkeyFromScancontext; AggregateSubmapScan :264-290).
+ * Scan k is points[3 scan_start[k] .. 3 scan_start[k+1]), packed xyz in the lidar frame.  Aggregate a is the union of its members
+ * [member_start[a], member_start[a+1]); member m is scan member_scan[m] (a scan may serve many members) through member_T[m] (12 doubles,
+ * row-major 3 x 4: T_ScanCenter_ScanToAgg of :280; member_T NULL: every member the identity).  T p is ((T0 x + T1 y) + T2 z) + T3 per
+ * row, no product fused.  For a transformed point (x, y, z): r = sqrt(x^2 + y^2); the point is dropped if r > max_radius (or if the
+ * transform took r or z out of the finite range); ring = clamp(ceil(r / max_radius * 20), 1, 20) - 1; sector = k for an azimuth
+ * (counter-clockwise from +x) in (6 k, 6 (k + 1)] degrees, azimuth 0 and r == 0 going to sector 0.  The sector is decided by
+ * comparisons of |y| against tan(6 m degrees) |x| (and the reverse above 45 degrees), never by atan: at a boundary the decision of
+ * sc_sector (csrc/scan_context.h) is the contract.  A bin's value is the maximum of z + lidar_height over its points; a bin without a
+ * point is 0.  NOT MODELLED: the original marks empty bins with -1000 and so also zeroes a bin whose maximum is exactly -1000.
+ * desc: 20 x 60 per aggregate, ring-major; ring_key (optional, 20): the mean of each row; sector_key (optional, 60): the mean of each
+ * column; n_binned (optional): the number of points kept.  An aggregate with no member or no point inside the radius is all zeros.
+ * n_aggregates == 0 does nothing.  INVALID: NULL where an array is needed, a start table that does not begin at 0 or decreases, a
+ * member index out of range, a non-finite point or transform entry, max_radius not positive and finite, a non-finite lidar_height.
+ * UNSUPPORTED: a scan of more than BSGPU_SC_MAX_SCAN_POINTS points.
+ *
+ * bsgpu_scan_context_match (detectLoopClosureID :141, distanceBtnScanContext, fastAlignUsingVkey, distDirectSC).  Set s is one
+ * SCManager of :120-132: queries [query_start[s], query_start[s+1]) of query_desc against candidates [cand_start[s], ..) of cand_desc
+ * (20 x 60 each, as describe writes them; keys and column norms are recomputed from them).  For a query q and a candidate c:
+ *   alignment     shift0 = the s in 0 .. 59 that minimises |sector_key(q) - circshift(sector_key(c), s)| (compared as squared norms),
+ *                 the first minimum winning; circshift moves column i to column (i + s) mod 60.
+ *   refinement    the shifts shift0 +- 0 .. R modulo 60 in ascending order, R = round(0.5 search_ratio 60) (3 at the shipped 0.1;
+ *                 R >= 30: all 60).  Per shift d = 1 - (1/n) sum_j cos(col_j(q), col_j(shifted c)) over the n columns that are non-zero
+ *                 on both sides; the first minimum wins.  A shift with n == 0 has distance +infinity (the library's choice: the
+ *                 original divides by zero).  Wherever values are compared (alignment norms, shift distances, ring-key
+ *                 distances) a NaN, which finite entries near the ends of the FP64 range can make, counts as +infinity.
+ *   pre-selection n_tree_candidates = K > 0: only the K candidates of the set nearest in squared ring-key distance are compared, ties
+ *                 to the lowest index (the k-d tree's NUM_CANDIDATES_FROM_TREE = 10 nearest of the original, done exactly).  K <= 0 or
+ *                 K at or above the set's size: all of them.
+ * Per query: the compared candidate of least (distance, index): best_cand (its index inside its set; -1 when that distance is not
+ * < dist_thres or the set has no candidate), best_dist and best_shift (still those of the best compared candidate; +infinity and 0
+ * when there is none), yaw (optional) = best_shift 2 pi / 60.  dist_all / shift_all (optional): every (query, candidate of its set)
+ * entry, queries in order and a query's candidates in order; +infinity and 0 for candidates that the pre-selection left out.
+ * NOT MODELLED: NUM_EXCLUDE_RECENT (the reference passes 0 and a caller chooses its candidate range) and the tree-rebuild period.
+ * The 60-term sums (means, key norms, the sum of cosines) have one fixed tree and the 20-term sums one fixed chain
+ * (csrc/scan_context.h), so an item's results never depend on the other items of the call, bit for bit.
+ * INVALID: NULL where an array is needed, bad start tables, non-finite descriptor entries, a negative or NaN search_ratio or
+ * dist_thres.  UNSUPPORTED: more than BSGPU_SC_MAX_CANDIDATES candidates in a set, K > BSGPU_SC_MAX_TREE_CANDIDATES.
+ * Both: nothing is written unless the call succeeds; bsgpu_scan_context_error says what this thread's last failed call objected to.  */
+#define BSGPU_SC_RINGS 20
+#define BSGPU_SC_SECTORS 60
+#define BSGPU_SC_MAX_CANDIDATES 65536
+#define BSGPU_SC_MAX_TREE_CANDIDATES 64
+#define BSGPU_SC_MAX_SCAN_POINTS (65535 * 4096)
+int bsgpu_scan_context_describe(int device, int32_t n_scans, const int32_t* scan_start, const double* points, int32_t n_aggregates,
+                                const int32_t* member_start, const int32_t* member_scan, const double* member_T, double lidar_height,
+                                double max_radius, double* desc, double* ring_key, double* sector_key, int32_t* n_binned);
+int bsgpu_scan_context_match(int device, int32_t n_sets, const int32_t* query_start, const double* query_desc, const int32_t* cand_start,
+                             const double* cand_desc, int32_t n_tree_candidates, double search_ratio, double dist_thres,
+                             int32_t* best_cand, double* best_dist, int32_t* best_shift, double* yaw, double* dist_all,
+                             int32_t* shift_all);
+const char* bsgpu_scan_context_error(void);
+
 /* Landmark triangulation for a batch of feature tracks at the context's CURRENT values (after a solve: the values the
  * solve left on the device) — VisualOdometry::TriangulateLandmark (bs_models/src/visual_odometry.cpp:532-610) and
  * SLAMInitialization::TriangulateLandmark (bs_models/src/slam_initialization.cpp:699-701), i.e. the [EXT]
