@@ -115,7 +115,7 @@ SYMBOLS = [
     "reprojection_errors", "preintegrate", "triangulate", "time_reproj_jacobian_ms", "reproj_jacobian_bytes", "dense_solve", "plan_info",
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
     "covariance_requests", "localize_frames", "num_factorizations", "essential_ransac", "absolute_pose_ransac",
-    "relative_pose_ransac", "inertial_alignment", "register_scans", "register_scans_error", "backsub_tangent_table",
+    "relative_pose_ransac", "inertial_alignment", "register_scans", "register_scans_error", "register_scans_gicp", "backsub_tangent_table",
     "scan_context_describe", "scan_context_match", "scan_context_error",
 ]
 
@@ -147,6 +147,15 @@ ICP_MAX_CELLS, ICP_MAX_ITER = 1 << 22, 1000
 ICP_DEFAULTS = dict(max_corr=1.0, max_iter=50, t_eps=1e-8, fit_eps=1e-2, rotation_threshold=0.99999, rel_mse_eps=1e-5)
 REGISTER_SCANS_ARGTYPES = [C.c_int, C.c_int32, _ip, _dp, _ip, _dp, _dp, C.c_double, C.c_int32, C.c_double, C.c_double, C.c_double,
                            C.c_double, _dp, _dp, _dp, _ip, _ip, _ip]
+#: bsgpu_register_scans_gicp: per-pair status values, the limits, the parameters (k_neighbors, max_iter, r_eps: the reference's
+#: config/matchers/gicp.json; gicp_epsilon, max_corr, t_eps, max_inner: PCL's GICP constructor, recalled; inner_eps, grid_cell: this
+#: library's own, grid_cell a performance knob that no result depends on) and the typed prototype
+GICP_MAX_ITERATIONS, GICP_TRANSFORM, GICP_TOO_FEW_CORRESPONDENCES, GICP_DEGENERATE = 1, 2, 5, 6
+GICP_MAX_K, GICP_MAX_INNER = 32, 64
+GICP_DEFAULTS = dict(k_neighbors=10, gicp_epsilon=1e-3, max_corr=5.0, max_iter=100, r_eps=1e-8, t_eps=5e-4, max_inner=20, inner_eps=1e-10,
+                     grid_cell=0.5)
+REGISTER_SCANS_GICP_ARGTYPES = [C.c_int, C.c_int32, _ip, _dp, _ip, _dp, _dp, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double,
+                                C.c_double, C.c_int32, C.c_double, C.c_double, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _dp, _dp]
 #: bsgpu_scan_context_describe / bsgpu_scan_context_match: the descriptor's shape, the limits, the reference's shipped parameters
 #: (SCManager's LIDAR_HEIGHT, PC_MAX_RADIUS, NUM_CANDIDATES_FROM_TREE, SEARCH_RATIO, SC_DIST_THRES, recalled) and the typed prototypes
 SC_RINGS, SC_SECTORS, SC_MAX_CANDIDATES, SC_MAX_TREE_CANDIDATES, SC_MAX_SCAN_POINTS = 20, 60, 65536, 64, 65535 * 4096

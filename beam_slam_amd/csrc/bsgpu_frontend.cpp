@@ -1,5 +1,5 @@
 // The front-end entry points of the C-ABI (include/bsgpu.h): bsgpu_preintegrate, bsgpu_inertial_alignment, bsgpu_register_scans,
-// bsgpu_scan_context_describe, bsgpu_scan_context_match, bsgpu_triangulate, bsgpu_localize_frames and the three RANSACs.  Each checks its arguments, describes its arrays as a StageLayout (staging.h:
+// bsgpu_register_scans_gicp, bsgpu_scan_context_describe, bsgpu_scan_context_match, bsgpu_triangulate, bsgpu_localize_frames and the three RANSACs.  Each checks its arguments, describes its arrays as a StageLayout (staging.h:
 // [inputs | outputs | scratch] in one device allocation), runs one kernel between one copy in and one copy out, and hands the
 // results to the caller's arrays: nothing is written to them unless the call succeeds.
 #include <algorithm>
@@ -7,6 +7,7 @@
 #include <string>
 
 #include "bsgpu_ctx.h"
+#include "gicp.h"
 #include "icp.h"
 #include "inertial_align.h"
 #include "scan_context.h"
@@ -190,6 +191,137 @@ int bsgpu_register_scans(int device, int32_t n_pairs, const int32_t* ref_start, 
   return BSGPU_OK;
 } catch (...) {
   try { g_register_scans_error = "register_scans: out of host memory"; } catch (...) {}
+  return api_exception(nullptr);
+}
+
+int bsgpu_register_scans_gicp(int device, int32_t n_pairs, const int32_t* ref_start, const double* ref_points, const int32_t* tgt_start,
+                              const double* tgt_points, const double* T_init, int32_t k_neighbors, double gicp_epsilon, double max_corr,
+                              int32_t max_iter, double r_eps, double t_eps, int32_t max_inner, double inner_eps, double grid_cell,
+                              double* T_refest_ref, double* T_ref_tgt, double* cost, int32_t* n_corr, int32_t* n_iters, int32_t* n_inner,
+                              int32_t* status, double* ref_cov, double* tgt_cov) try {
+  const auto refuse = [](int code, const char* why) { g_register_scans_error = why; return code; };
+  if (n_pairs < 0 || !ref_start || !tgt_start || !T_refest_ref || !status) return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: null argument");
+  if (k_neighbors < 1) return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: k_neighbors must be at least 1");
+  if (!(gicp_epsilon > 0.0) || !(gicp_epsilon <= 1.0)) return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: gicp_epsilon must lie in (0, 1]");
+  if (!(max_corr > 0.0) || !std::isfinite(max_corr)) return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: max_corr must be positive and finite");
+  if (!(grid_cell > 0.0) || !std::isfinite(grid_cell)) return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: grid_cell must be positive and finite");
+  if (max_iter < 1) return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: max_iter must be at least 1");
+  if (max_inner < 1) return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: max_inner must be at least 1");
+  if (!(r_eps >= 0.0) || !(t_eps >= 0.0) || !(inner_eps >= 0.0))
+    return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: r_eps, t_eps and inner_eps must not be negative or NaN");
+  if (k_neighbors > BSGPU_GICP_MAX_K) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans_gicp: k_neighbors exceeds BSGPU_GICP_MAX_K");
+  if (max_iter > BSGPU_ICP_MAX_ITER) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans_gicp: max_iter exceeds BSGPU_ICP_MAX_ITER");
+  if (max_inner > BSGPU_GICP_MAX_INNER) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans_gicp: max_inner exceeds BSGPU_GICP_MAX_INNER");
+  static_assert(BSGPU_GICP_MAX_K == kGicpMaxK && BSGPU_GICP_MAX_INNER == kGicpMaxInner, "the header's caps are gicp.h's");
+  const auto finite_items = [](const int32_t* start, const double* pts) {
+    return [start, pts](int k) {
+      if (start[k + 1] > start[k] && !pts) return false;
+      for (size_t i = 3 * (size_t)start[k]; i < 3 * (size_t)start[k + 1]; ++i) if (!std::isfinite(pts[i])) return false;
+      return true;
+    };
+  };
+  switch (check_start_table(ref_start, n_pairs, INT_MAX, finite_items(ref_start, ref_points))) {
+    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: ref_start[0] must be 0");
+    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: ref_start must be non-decreasing");
+    case kStartBadItem: return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: null or non-finite reference points");
+    default: break;
+  }
+  switch (check_start_table(tgt_start, n_pairs, INT_MAX, finite_items(tgt_start, tgt_points))) {
+    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: tgt_start[0] must be 0");
+    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: tgt_start must be non-decreasing");
+    case kStartBadItem: return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: null or non-finite target points");
+    default: break;
+  }
+  const size_t np = (size_t)n_pairs;
+  const size_t n_ref = (size_t)ref_start[n_pairs], n_tgt = (size_t)tgt_start[n_pairs], n_pts = n_ref + n_tgt;
+  if (n_pts > (size_t)INT_MAX) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans_gicp: more than 2^31 - 1 points in one call");
+  // the call's clouds as one packed array: the targets of all pairs, then the sources; a source's transform is the identity
+  static const double eye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+  std::vector<double> T_cloud(24 * np), pts(3 * n_pts);
+  std::vector<int32_t> cloud_start(2 * np + 1, 0), chunk_start(np + 1, 0);
+  for (size_t i = 0; i < 12 * np; ++i) {
+    T_cloud[i] = T_init ? T_init[i] : eye[i % 12];
+    T_cloud[12 * np + i] = eye[i % 12];
+    if (!std::isfinite(T_cloud[i])) return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: non-finite T_init");
+  }
+  if (n_tgt) std::memcpy(pts.data(), tgt_points, 24 * n_tgt);
+  if (n_ref) std::memcpy(pts.data() + 3 * n_tgt, ref_points, 24 * n_ref);
+  for (size_t p = 0; p < np; ++p) {
+    cloud_start[p + 1] = tgt_start[p + 1];
+    cloud_start[np + p + 1] = (int32_t)n_tgt + ref_start[p + 1];
+  }
+  // the grids: the bounding box of every cloud in the frame it is searched in, by the arithmetic the device will use (icp.h)
+  std::vector<IcpGrid> grids(2 * np);
+  double cells = 0.0;
+  int max_points = 0, max_chunks = 0, n_live = 0;
+  for (size_t c = 0; c < 2 * np; ++c) {
+    IcpGrid& g = grids[c];
+    g.h = grid_cell; g.cell0 = (int)cells;
+    for (int a = 0; a < 3; ++a) { g.o[a] = 0.0; g.n[a] = 0; }
+    const int n = cloud_start[c + 1] - cloud_start[c];
+    max_points = std::max(max_points, n);
+    if (n == 0) continue;
+    double lo[3], hi[3], q[3];
+    for (int i = 0; i < n; ++i) {
+      icp_apply(&T_cloud[12 * c], &pts[3 * ((size_t)cloud_start[c] + i)], q);
+      for (int a = 0; a < 3; ++a) { lo[a] = i == 0 || q[a] < lo[a] ? q[a] : lo[a]; hi[a] = i == 0 || q[a] > hi[a] ? q[a] : hi[a]; }
+    }
+    double nc[3], here = 1.0;
+    for (int a = 0; a < 3; ++a) {
+      if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: T_init takes a target point out of range");
+      nc[a] = icp_axis_cells(lo[a], hi[a], grid_cell);
+      here *= nc[a];
+    }
+    if (!(here <= (double)BSGPU_ICP_MAX_CELLS)) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans_gicp: a cloud's grid exceeds BSGPU_ICP_MAX_CELLS cells");
+    cells += here;
+    if (cells > 16.0 * BSGPU_ICP_MAX_CELLS) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans_gicp: the call's grids exceed 16 x BSGPU_ICP_MAX_CELLS cells");
+    for (int a = 0; a < 3; ++a) { g.o[a] = lo[a]; g.n[a] = (int)nc[a]; }
+  }
+  for (size_t p = 0; p < np; ++p) {
+    const int ns = ref_start[p + 1] - ref_start[p], nt = tgt_start[p + 1] - tgt_start[p], chunks = (ns + kIcpChunk - 1) / kIcpChunk;
+    chunk_start[p + 1] = chunk_start[p] + chunks;
+    max_chunks = std::max(max_chunks, chunks);
+    n_live += ns >= k_neighbors && nt >= k_neighbors ? 1 : 0;
+  }
+  if (n_pairs == 0) return BSGPU_OK;
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "register_scans_gicp: hipSetDevice failed"); }
+  const size_t n_chunks = (size_t)chunk_start[n_pairs];
+  const int n_tiles = (int)(((size_t)cells + kIcpScanTile - 1) / kIcpScanTile);
+  StageLayout L;
+  const int s_cs = L.in(cloud_start.data(), 4 * (2 * np + 1)), s_pts = L.in(pts.data(), 24 * n_pts), s_tc = L.in(T_cloud.data(), 192 * np),
+            s_ch = L.in(chunk_start.data(), 4 * (np + 1)), s_gr = L.in(grids.data(), sizeof(IcpGrid) * 2 * np);
+  const int s_T = L.out(T_refest_ref, 96 * np), s_Trt = L.out(T_ref_tgt, 96 * np), s_cost = L.out(cost, 8 * np), s_nc = L.out(n_corr, 4 * np),
+            s_ni = L.out(n_iters, 4 * np), s_nn = L.out(n_inner, 4 * np), s_st = L.out(status, 4 * np),
+            s_cov = L.out(nullptr, ref_cov || tgt_cov ? 48 * n_pts : 0);
+  // the kernels' working arrays (uninitialised): the grid build's, the covariances when nobody asked for them, the pairs' states and
+  // done words, j(i) and M_i per point, the chunks' kept counts and partial records
+  const int s_tq = L.scratch(24 * n_pts), s_cell = L.scratch(4 * n_pts), s_cells = L.scratch(4 * (size_t)n_tiles * kIcpScanTile),
+            s_tile = L.scratch(4 * (size_t)n_tiles), s_rec = L.scratch(32 * n_pts), s_gT = L.scratch(192 * np), s_gp = L.scratch(16 * np),
+            s_gd = L.scratch(8 * np), s_cov2 = L.scratch(ref_cov || tgt_cov ? 0 : 48 * n_pts), s_state = L.scratch(sizeof(GicpState) * np),
+            s_done = L.scratch(4 * np), s_corr = L.scratch(4 * n_pts), s_M = L.scratch(48 * n_pts), s_kept = L.scratch(4 * n_chunks),
+            s_part = L.scratch(8 * kGicpRec * n_chunks);
+  DeviceStage D(L);
+  if (!D) return refuse(BSGPU_ERR_DEVICE, "register_scans_gicp: out of device memory");
+  const GicpParams P{k_neighbors, gicp_epsilon, max_corr, max_iter, r_eps, t_eps, max_inner, inner_eps};
+  const auto F = [&](int s) { return D.ptr<double>(s); };
+  const auto I = [&](int s) { return D.ptr<int>(s); };
+  hipError_t le = hipSuccess;
+  const hipError_t e = D.run(nullptr, [&] {
+    le = launch_register_scans_gicp(nullptr, n_pairs, n_live, max_points, (int)n_pts, max_chunks, n_tiles, I(s_cs), F(s_pts), F(s_tc), I(s_ch),
+                                    D.ptr<IcpGrid>(s_gr), P, F(s_T), F(s_Trt), F(s_cost), I(s_nc), I(s_ni), I(s_nn), I(s_st),
+                                    F(ref_cov || tgt_cov ? s_cov : s_cov2), F(s_tq), I(s_cell), I(s_cells), I(s_tile), F(s_rec), F(s_gT), F(s_gp),
+                                    I(s_gd), D.ptr<GicpState>(s_state), I(s_done), I(s_corr), F(s_M), I(s_kept), F(s_part));
+  });
+  if (e != hipSuccess || le != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "register_scans_gicp: device error"); }
+  L.scatter();
+  if (ref_cov || tgt_cov) {
+    const double* cov = L.out_image<double>(s_cov);
+    if (tgt_cov && n_tgt) std::memcpy(tgt_cov, cov, 48 * n_tgt);
+    if (ref_cov && n_ref) std::memcpy(ref_cov, cov + 6 * n_tgt, 48 * n_ref);
+  }
+  return BSGPU_OK;
+} catch (...) {
+  try { g_register_scans_error = "register_scans_gicp: out of host memory"; } catch (...) {}
   return api_exception(nullptr);
 }
 

@@ -202,10 +202,10 @@ __global__ __launch_bounds__(64) void icp_update_kernel(int k, const int* chunk_
   }
 }
 
-void launch_register_scans(hipStream_t s, int n_pairs, int max_targets, int n_targets, int max_chunks, int n_tiles, const int* ref_start,
-                           const double* ref, const int* tgt_start, const double* tgt, const double* T_init, const int* chunk_start,
-                           const IcpGrid* grids, double max_corr, const IcpParams& P, double* T, double* T_ref_tgt, double* mse, int* n_corr,
-                           int* n_iters, int* status, double* tq, int* tcell, int* cells, int* tile_sum, double* rec, double* part,
+// The grids of n_pairs clouds (the once-per-call launches above), also for bsgpu_register_scans_gicp (k_gicp.hip), whose clouds are
+// the targets and the sources of its pairs.
+void launch_icp_grid_build(hipStream_t s, int n_pairs, int max_targets, int n_targets, int n_tiles, const int* tgt_start, const double* tgt,
+                           const double* T_init, const IcpGrid* grids, double* tq, int* tcell, int* cells, int* tile_sum, double* rec, double* T,
                            double* mse_prev, int* done) {
   if (n_pairs <= 0) return;
   const int prep_x = std::max(1, std::min((max_targets + kIcpPrepThreads - 1) / kIcpPrepThreads, 1024));
@@ -218,6 +218,15 @@ void launch_register_scans(hipStream_t s, int n_pairs, int max_targets, int n_ta
     hipLaunchKernelGGL(icp_scan_cells_kernel, dim3(n_tiles), dim3(kIcpScanThreads), 0, s, reinterpret_cast<int4*>(cells), tile_sum);
     hipLaunchKernelGGL(icp_scatter_kernel, dim3(prep_x, n_pairs), dim3(kIcpPrepThreads), 0, s, tgt_start, tq, tcell, cells, rec, n_targets);
   }
+}
+
+void launch_register_scans(hipStream_t s, int n_pairs, int max_targets, int n_targets, int max_chunks, int n_tiles, const int* ref_start,
+                           const double* ref, const int* tgt_start, const double* tgt, const double* T_init, const int* chunk_start,
+                           const IcpGrid* grids, double max_corr, const IcpParams& P, double* T, double* T_ref_tgt, double* mse, int* n_corr,
+                           int* n_iters, int* status, double* tq, int* tcell, int* cells, int* tile_sum, double* rec, double* part,
+                           double* mse_prev, int* done) {
+  if (n_pairs <= 0) return;
+  launch_icp_grid_build(s, n_pairs, max_targets, n_targets, n_tiles, tgt_start, tgt, T_init, grids, tq, tcell, cells, tile_sum, rec, T, mse_prev, done);
   const double h2 = max_corr * max_corr;
   for (int k = 1; k <= P.max_iter; ++k) {
     if (max_chunks > 0)

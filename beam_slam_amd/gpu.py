@@ -137,6 +137,42 @@ def register_scans(ref_start, ref_points, tgt_start, tgt_points, T_init=None, ma
     return out
 
 
+def register_scans_gicp(ref_start, ref_points, tgt_start, tgt_points, T_init=None, k_neighbors=capi.GICP_DEFAULTS["k_neighbors"],
+                        gicp_epsilon=capi.GICP_DEFAULTS["gicp_epsilon"], max_corr=capi.GICP_DEFAULTS["max_corr"],
+                        max_iter=capi.GICP_DEFAULTS["max_iter"], r_eps=capi.GICP_DEFAULTS["r_eps"], t_eps=capi.GICP_DEFAULTS["t_eps"],
+                        max_inner=capi.GICP_DEFAULTS["max_inner"], inner_eps=capi.GICP_DEFAULTS["inner_eps"],
+                        grid_cell=capi.GICP_DEFAULTS["grid_cell"], covariances=True, device=0):
+    """bsgpu_register_scans_gicp: Generalized ICP (the reference's matcher in its shipped GICP configuration) for a batch of scan pairs,
+    clouds and roles as in register_scans.  Returns a dict of arrays: T_refest_ref and T_ref_tgt (P x 3 x 4), cost, n_corr, n_iters,
+    n_inner, status (P) and, unless covariances is false, ref_cov and tgt_cov (6 per point: xx, xy, xz, yy, yz, zz)."""
+    import numpy as np
+    rs = np.ascontiguousarray(ref_start, np.int32).reshape(-1)
+    ts = np.ascontiguousarray(tgt_start, np.int32).reshape(-1)
+    rp = np.ascontiguousarray(ref_points, np.float64).reshape(-1, 3)
+    tp = np.ascontiguousarray(tgt_points, np.float64).reshape(-1, 3)
+    P = rs.size - 1
+    ti = None if T_init is None else np.ascontiguousarray(T_init, np.float64).reshape(-1, 3, 4)
+    if P < 0 or ts.size != P + 1 or (ti is not None and ti.shape[0] != P):
+        raise capi.SolverError(capi.ERR_INVALID, "register_scans_gicp: array sizes do not agree")
+    if int(rs.max()) > rp.shape[0] or int(ts.max()) > tp.shape[0]:
+        raise capi.SolverError(capi.ERR_INVALID, "register_scans_gicp: ref_start / tgt_start name more points than were passed")
+    out = dict(T_refest_ref=np.zeros((P, 3, 4)), T_ref_tgt=np.zeros((P, 3, 4)), cost=np.zeros(P), n_corr=np.zeros(P, np.int32),
+               n_iters=np.zeros(P, np.int32), n_inner=np.zeros(P, np.int32), status=np.zeros(P, np.int32))
+    if covariances:
+        out.update(ref_cov=np.zeros((max(int(rs[-1]), 0), 6)), tgt_cov=np.zeros((max(int(ts[-1]), 0), 6)))
+    fn = lib().bsgpu_register_scans_gicp
+    fn.argtypes = capi.REGISTER_SCANS_GICP_ARGTYPES
+    _dp, _ip = capi._dp, capi._ip
+    d = lambda x: None if x is None else x.ctypes.data_as(_dp)
+    i = lambda x: x.ctypes.data_as(_ip)
+    rc = fn(device, P, i(rs), d(rp), i(ts), d(tp), d(ti), int(k_neighbors), float(gicp_epsilon), float(max_corr), int(max_iter), float(r_eps),
+            float(t_eps), int(max_inner), float(inner_eps), float(grid_cell), d(out["T_refest_ref"]), d(out["T_ref_tgt"]), d(out["cost"]),
+            i(out["n_corr"]), i(out["n_iters"]), i(out["n_inner"]), i(out["status"]), d(out.get("ref_cov")), d(out.get("tgt_cov")))
+    if rc != 0:
+        raise capi.SolverError(rc, register_scans_error())
+    return out
+
+
 def register_scans_error():
     """What this thread's last failed bsgpu_register_scans objected to."""
     fn = lib().bsgpu_register_scans_error

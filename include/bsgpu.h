@@ -577,6 +577,58 @@ int bsgpu_register_scans(int device, int32_t n_pairs, const int32_t* ref_start, 
                          double* mse, int32_t* n_corr, int32_t* n_iters, int32_t* status);
 const char* bsgpu_register_scans_error(void);
 
+/* Generalized ICP for a batch of scan pairs — the matcher_->Match() of RelocCandidateSearchScanContext::AlignSubmapsFromScanMatches
+ * (bs_models/src/lib/reloc/reloc_candidate_search_scan_context.cpp:210-262; the same GicpMatcher in submap_alignment.cpp:52,
+ * global_map_batch_optimization.cpp:48, scan_registration_base.cpp:88 and RelocRefinementScanRegistration<GicpMatcher>) in the shipped
+ * GICP configuration (config/matchers/gicp.json: corr_rand 10, max_iter 100, r_eps 1e-8, fit_eps 1e-2, res 0.1).  [EXT] libbeam's
+ * GicpMatcher and PCL's GeneralizedIterativeClosestPoint are not in the reference checkout: what is taken from them below (the
+ * covariances, the correspondence rule, the objective, the outer criterion, the constructor's defaults) is RECALLED, not verified, and
+ * everything is computed in FP64.  PCL's GICP loop does not read fit_eps (recalled), so it is no parameter.  res, the matcher's voxel
+ * downsampling, is the caller's job: the clouds are registered as they are passed.
+ * Clouds and roles as in bsgpu_register_scans: S the reference cloud (SetRef, PCL's source), Q the target cloud after T_init (optional,
+ * 12 doubles per pair, row-major 3 x 4; NULL: the identity) has been applied to it on the device.
+ *   covariances       (PCL's computeCovariances) once per cloud per call.  For a point p of a cloud P, |P| >= k_neighbors = k: its k
+ *                     nearest points of P, itself included, in ascending (d^2, index) order; mu their mean; C = (1/k) sum (x - mu)
+ *                     (x - mu)^T (PCL: E[x x^T] - mu mu^T; the centred form is the library's choice); its eigen-decomposition with
+ *                     eigenvalues in falling order; C' = u1 u1^T + u2 u2^T + gicp_epsilon u3 u3^T.  The target's are those of Q.
+ *                     ref_cov, tgt_cov (optional): C' as 6 doubles per point (xx, xy, xz, yy, yz, zz); zeros for a pair that has a
+ *                     cloud of fewer than k points.
+ *   outer iteration   k = 1 .. max_iter from T = I.  Per source point s = T S_i, j(i) the nearest point of Q by (d^2, index), kept iff
+ *                     d^2 < max_corr^2 (strict, as recalled from PCL's nn_dists[0] < dist_threshold); M_i = (C'^Q_j + R C'^S_i R^T)^-1
+ *                     with R from T at the start of this outer iteration.  Fewer than 4 kept: TOO_FEW_CORRESPONDENCES, T stays.
+ *   inner loop        at most max_inner steps that minimise F(T) = sum r_i^T M_i r_i, r_i = T S_i - q_j(i), correspondences and M_i
+ *                     fixed: plain Gauss-Newton with a left update, J = [-[s]x | I], H = sum J^T M J, g = sum J^T M r, xi = -H^-1 g by
+ *                     a 6 x 6 Cholesky, T <- [exp(w) | v] T with Rodrigues' formula for w.  It stops after the step whose
+ *                     max |xi| < inner_eps.  A pivot <= 1e-12 x that diagonal entry of H ends the pair with BSGPU_GICP_DEGENERATE, T as it
+ *                     was before this outer iteration.  PCL minimises the same objective with BFGS over (x, y, z, roll, pitch, yaw): its
+ *                     iterates are NOT reproduced; the objective, the correspondences, the covariances and the outer criterion are.
+ *   outer criterion   (PCL's delta rule, recalled) with T0 the transform before this outer iteration,
+ *                     delta = max(max_kl |R - R0|_kl / r_eps, max_k |t - t0|_k / t_eps): k >= max_iter: MAX_ITERATIONS (counts as converged,
+ *                     checked first, as in ICP); otherwise delta < 1: TRANSFORM.
+ * A cloud of fewer than k_neighbors points, an empty one included: TOO_FEW_CORRESPONDENCES with T = I and n_iters = 0 (PCL refuses such
+ * a cloud, recalled).
+ * Both neighbour queries — the k nearest of a cloud in itself, no radius, and the nearest target below max_corr — are exact, ties
+ * decided by (d^2, index): a dense grid of cell edge grid_cell over each cloud's bounding box (one for S, used by its covariances
+ * only, and one for Q) is searched in shells of cells around the query's cell until nothing that has not been searched can matter.
+ * grid_cell is a performance knob only: no result, covariances included, depends on it, bit for bit.  The sums have a fixed order, so
+ * a pair's results never depend on the other pairs of the call, bit for bit.
+ * Outputs per pair: T_refest_ref (12); T_ref_tgt (optional, 12: inv(T_refest_ref) T_init); cost (optional: F / n_corr of the last pass
+ * over the correspondences; 0 when there was none); n_corr (optional: kept in the last outer iteration); n_iters (optional: outer
+ * iterations applied); n_inner (optional: Gauss-Newton steps in total); status (BSGPU_GICP_*; converged iff MAX_ITERATIONS or
+ * TRANSFORM).  n_pairs == 0 does nothing.
+ * UNSUPPORTED: k_neighbors > BSGPU_GICP_MAX_K; a grid of more than BSGPU_ICP_MAX_CELLS cells; grids that together hold more than 16 times
+ * as many; max_iter > BSGPU_ICP_MAX_ITER; max_inner > BSGPU_GICP_MAX_INNER.  INVALID: what bsgpu_register_scans refuses, and k_neighbors
+ * < 1, max_inner < 1, gicp_epsilon outside (0, 1], grid_cell not positive and finite, a negative or NaN r_eps, t_eps or inner_eps.
+ * Nothing is written unless the call succeeds; bsgpu_register_scans_error says what this thread's last failed call objected to.  */
+enum { BSGPU_GICP_MAX_ITERATIONS = 1, BSGPU_GICP_TRANSFORM = 2, BSGPU_GICP_TOO_FEW_CORRESPONDENCES = 5, BSGPU_GICP_DEGENERATE = 6 };
+#define BSGPU_GICP_MAX_K 32
+#define BSGPU_GICP_MAX_INNER 64
+int bsgpu_register_scans_gicp(int device, int32_t n_pairs, const int32_t* ref_start, const double* ref_points, const int32_t* tgt_start,
+                              const double* tgt_points, const double* T_init, int32_t k_neighbors, double gicp_epsilon, double max_corr,
+                              int32_t max_iter, double r_eps, double t_eps, int32_t max_inner, double inner_eps, double grid_cell,
+                              double* T_refest_ref, double* T_ref_tgt, double* cost, int32_t* n_corr, int32_t* n_iters, int32_t* n_inner,
+                              int32_t* status, double* ref_cov, double* tgt_cov);
+
 /* Scan Context place recognition — the descriptors and the search of RelocCandidateSearchScanContext::FindRelocCandidates
  * (bs_models/src/lib/reloc/reloc_candidate_search_scan_context.cpp:117-150): the step that decides which scan pairs
  * AlignSubmapsFromScanMatches (:210-262) hands to the matcher (bsgpu_register_scans).  Two stateless calls, so that a caller can keep
