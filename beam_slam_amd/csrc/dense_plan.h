@@ -66,7 +66,7 @@ constexpr int kFusedSplit = 256;    // ONE K-CHUNK of the LAST update of a tile 
                                     // Such an update is dealt out to 4 (5 with an appendix) workgroups: chunk p forms the 16 columns 16 p .. of X_ti / X_tj
                                     // (W = L_kk^-1 is lower triangular: K = 16 (p + 1)) and ADDS their rank-16 product to the tile with FP64 atomics once
                                     // every earlier update of the tile has been published (need_c = that count: the chunks share one turn, the last); the
-                                    // appendix chunk forms the appendix's 16 columns.  tot_c = chunk | number of chunks << 8.  The tile's counter counts the
+                                    // appendix chunk forms the appendix's 16 columns.  tot_c = chunk | number of chunks << 8 | place among the tile's chunks << 16.  The tile's counter counts the
                                     // chunks in its upper half: tile_tot = updates with a turn of their own | chunks << 16.  (The order in which the chunks'
                                     // sums reach a tile varies: the factor is reproducible to rounding, like the assembled system it factors.)
 constexpr int kFusedRowSeg = 512;   // SEVERAL updates of one row tile by one panel in one task (ftasks_rows; k_chol.hip chol_fused_rowseg): tj = index of the segment's first
@@ -642,7 +642,7 @@ struct DensePlan {
           if ((f.flags & (kFusedChain | kFusedRider)) || f.need_c < 0) continue;
           updaters[(size_t)f.ti * N + f.tj].push_back(t);
         }
-        std::vector<int> n_chunks(nt, 0), turn(nt, 0);
+        std::vector<int> n_chunks(nt, 0), turn(nt, 0), chunk_base(nt, 0);
         for (int a = 0; a < T; ++a)
           for (int b = 0; b <= a; ++b) {
             if (fchain_of_tile[a] < 0 || fchain_of_tile[a] != fchain_of_tile[b]) continue;
@@ -656,7 +656,7 @@ struct DensePlan {
             }
             if (!taken) continue;
             const int lo = (int)u.size() - taken;   // the updates that keep a turn of their own: need_c 0 .. lo - 1
-            for (int q = lo; q < (int)u.size(); ++q) turn[u[q]] = lo;
+            for (int q = lo, base = 0; q < (int)u.size(); base += n_chunks[u[q]], ++q) { turn[u[q]] = lo; chunk_base[u[q]] = base; }
             n_split_chunks += hi;
             tile_tot[(size_t)a * N + b] = lo | (hi << 16);
           }
@@ -669,7 +669,7 @@ struct DensePlan {
               FusedTask f = ftasks[t];
               f.flags = (f.flags & (kFusedExt | kFusedPublishX)) | kFusedSplit;   // (a chunk forms its own columns of X: nothing published is read)
               f.need_c = turn[t];   // (the chunks of a tile share ONE turn, after every update that has a turn of its own)
-              f.tot_c = p | (n_chunks[t] << 8);
+              f.tot_c = p | (n_chunks[t] << 8) | ((chunk_base[t] + p) << 16);   // (bits 16..: its place among ALL chunks of the tile, in list order)
               nl.push_back(f);
             }
           }

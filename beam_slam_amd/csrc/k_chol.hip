@@ -718,9 +718,10 @@ BSG_DEV bool chol_fused_update(const FusedCtx& C, int t, const FusedTask& tk, do
       if (solve_j) ok = ok && wait_count(&upd[(tj * N + te) * fs], tot[(size_t)tj * N + te], abort_w, deadline);
     }
     s_ctl[1] = ok ? 1 : 0;
-    // ... and the C tile, if it is already this task's turn on it (on the critical path it is: the tile's earlier updaters are
-    // panels that finished long ago): its values wait in registers through the solves, and the product accumulates onto them
-    s_ctl[3] = (do_update && !no_turn && (tk.need_c == 0 || (ld_flag(&upd[(ti * N + tj) * fs]) & 0xffff) >= tk.need_c)) ? 1 : 0;
+    // ... and the C tile, if this task is the tile's first updater: its values wait in registers through the solves, and the product accumulates
+    // onto them.  (Only then: C - X X^T summed onto C and summed from zero and added to C round differently, and whether a later updater's turn has
+    // come by now is a matter of timing — the factor under turns is the same bits every run, so the plan decides which form a task takes, not the clock.)
+    s_ctl[3] = (do_update && !no_turn && tk.need_c == 0) ? 1 : 0;
   }
   __syncthreads();
   const bool c_pre = __builtin_amdgcn_readfirstlane(s_ctl[3]) != 0;
@@ -826,8 +827,8 @@ BSG_DEV bool chol_fused_update(const FusedCtx& C, int t, const FusedTask& tk, do
   double4_t acc[TPW];
 #pragma unroll
   for (int u = 0; u < TPW; ++u) acc[u] = double4_t{0.0, 0.0, 0.0, 0.0};
-  // The C tile: already in registers (requested before the wait for L_kk), or — if the turn had not come by then — one more look
-  // now: a tile requested here still travels under the 256 MFMAs instead of being waited for after them.
+  // The C tile of the tile's first updater under turns: already in registers (requested before the wait for L_kk); every other one is
+  // added at the task's turn, behind the product
   bool c_early = false;
   if (do_update) {
     if (c_pre) {
@@ -835,17 +836,6 @@ BSG_DEV bool chol_fused_update(const FusedCtx& C, int t, const FusedTask& tk, do
       if (strip_on) {
 #pragma unroll
         for (int u = 0; u < TPW; ++u) acc[u] = cpre[u];
-      }
-    } else if (!no_turn) {
-      if (tid == 0) s_ctl[3] = ((ld_flag(&upd[(ti * N + tj) * fs]) & 0xffff) >= tk.need_c) ? 1 : 0;
-      __syncthreads();
-      c_early = __builtin_amdgcn_readfirstlane(s_ctl[3]) != 0;
-      if (c_early && strip_on) {
-#pragma unroll
-        for (int u = 0; u < TPW; ++u)
-#pragma unroll
-          for (int reg = 0; reg < 4; ++reg)
-            acc[u][reg] = ld8_sc1(rS_i, (unsigned)(((size_t)(16 * rs + crow + 4 * reg) * ld + rj + 16 * (tt0 + u) + ccol) * sizeof(double)));
       }
     }
     if (strip_on) {
@@ -935,7 +925,8 @@ BSG_DEV double4_t mfma_ab_rt(double4_t acc, const double* sA, int lda, const dou
 }
 // ONE K-CHUNK of the last update of a tile inside a chain (dense_plan.h kFusedSplit): chunk p of P forms the 16 columns 16 p .. of
 // X_ti = A(ti, k) W^T (W = L_kk^-1 is lower triangular: K = 16 (p + 1)) and of X_tj and adds -X_ti X_tj^T (rank 16) to the tile with FP64
-// atomics, once the tile's earlier updates are all in (tk.need_c: the chunks share the last turn).  The appendix chunk (p = P - 1 of a panel
+// atomics, once the tile's earlier updates are all in (tk.need_c: the chunks share the last turn; in a launch with turns they take it one after another,
+// in list order: tk.tot_c bits 16..).  The appendix chunk (p = P - 1 of a panel
 // that carries an appendix) forms the appendix's columns X_e = E W16^T - A M^T with M = W16 L(k+1, k) W — the lower-left block of the
 // inverse of the 80-column factor, 16 x 64, formed here (20 MFMAs on the path instead of the whole strips' solves).  A diagonal task's
 // chunks publish their columns of X to the factor; the last one to have done so bumps the panel tile's counter (what the readers of X wait for).
@@ -966,7 +957,7 @@ BSG_DEV bool chol_fused_split(const FusedCtx& C, int t, const FusedTask& tk, dou
   auto stamp = [&](int sl) { if (PROBE && tid == 0) probe_ts[(size_t)t * 8 + sl] = wall_clock64(); };
   stamp(1);
   const int k = tk.k, ti = tk.ti, tj = tk.tj;
-  const int p = tk.tot_c & 0xff, P = tk.tot_c >> 8;
+  const int p = tk.tot_c & 0xff, P = (tk.tot_c >> 8) & 0xff, place = tk.tot_c >> 16;   // (place: among all chunks of the tile, in list order)
   const bool diag = ti == tj;
   const bool ext = (tk.flags & kFusedExt) != 0, ext_chunk = ext && p == P - 1;
   const int te = k + 1;
@@ -1105,9 +1096,10 @@ BSG_DEV bool chol_fused_split(const FusedCtx& C, int t, const FusedTask& tk, dou
       acc[u] = mfma_abt_rt(acc[u], sEi + (16 * rs) * kExtPitch, kExtPitch, Ej + (16 * (tt0 + u)) * kExtPitch, kExtPitch, -1.0, 16, lane);
   }
   // the chunks' turn: every earlier update of the tile has been published (on the critical path: long ago) — with no turns (chol_fused_update) only
-  // a diagonal tile's LM-diagonal task, which rewrites the tile
+  // a diagonal tile's LM-diagonal task, which rewrites the tile.  With turns the chunks of a tile add one after another too, in list order (the
+  // upper half of the tile's counter is the number of chunks that are in; an earlier chunk has an earlier ticket): the factor is the same bits every run
   const int no_turn = __builtin_amdgcn_readfirstlane(C.no_turn);
-  const int need_c = no_turn == 0 ? tk.need_c : (no_turn == 1 && diag ? (tk.need_c < 1 ? tk.need_c : 1) : 0);
+  const int need_c = no_turn == 0 ? (tk.need_c | (place << 16)) : (no_turn == 1 && diag ? (tk.need_c < 1 ? tk.need_c : 1) : 0);
   if (tid == 0) s_ctl[1] = wait_count(&upd[(ti * N + tj) * fs], need_c, abort_w, deadline) ? 1 : 0;
   __syncthreads();
   if (__builtin_amdgcn_readfirstlane(s_ctl[1]) == 0) return false;

@@ -155,7 +155,7 @@ static int replay_list(const DensePlan& P, const std::vector<uint8_t>& adj, unsi
     }
     if (f.flags & kFusedSplit) {
       // one K-chunk of an update of a tile inside a chain: its share of the product goes to a partial tile of its own, no turn
-      const int k = f.k, i = f.ti, j = f.tj, pch = f.tot_c & 0xff, Pn = f.tot_c >> 8;
+      const int k = f.k, i = f.ti, j = f.tj, pch = f.tot_c & 0xff, Pn = (f.tot_c >> 8) & 0xff, place = f.tot_c >> 16;
       const bool diag = i == j, ext = (f.flags & kFusedExt) != 0, ext_chunk = ext && pch == Pn - 1;
       ++g_split_tasks;
       if (Pn != kFusedSplitChunks + (ext ? 1 : 0) || pch < 0 || pch >= Pn) fail("chunk numbering", (int)t);
@@ -182,6 +182,7 @@ static int replay_list(const DensePlan& P, const std::vector<uint8_t>& adj, unsi
       }
       if (f.need_c != tot_lo(i, j) || upd[(size_t)i * N + j] != f.need_c) fail("chunk: the tile's updates with a turn of their own are not all in", (int)t);
       if (upd_hi[(size_t)i * N + j] >= tot_hi(i, j)) fail("chunk: more chunks than the tile counts", (int)t);
+      if (upd_hi[(size_t)i * N + j] != place) fail("chunk: not at its place among the tile's chunks", (int)t);   // (what a launch with turns waits for)
       S[(size_t)i * N + j] -= val;
       upd_hi[(size_t)i * N + j]++;
       if (f.flags & kFusedPublishX) {
