@@ -9,6 +9,7 @@
 #include "bsgpu_ctx.h"
 #include "gicp.h"
 #include "icp.h"
+#include "point_grid.h"
 #include "inertial_align.h"
 #include "scan_context.h"
 #include "staging.h"
@@ -18,6 +19,78 @@ using namespace bsg;
 namespace {
 thread_local std::string g_register_scans_error;   // what this thread's last failed bsgpu_register_scans objected to (it has no context to keep it)
 thread_local std::string g_scan_context_error;     // the same for bsgpu_scan_context_describe and bsgpu_scan_context_match
+
+// ---- what bsgpu_register_scans and bsgpu_register_scans_gicp share: a table of scan pairs, the grids of its clouds, its chunks ----------
+const double kEye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+int refuse_scans(int code, const char* prefix, const std::string& why) { g_register_scans_error = std::string(prefix) + ": " + why; return code; }
+
+// The pair table of a call: the two start tables, in check_start_table's order, an item bad when one of its points is not finite (a
+// NaN would choose a grid cell); init (12 per pair) <- T_init, the identity without one, which must be finite.  BSGPU_OK, or the
+// refusal with its message under the caller's prefix.
+int check_pair_table(const char* prefix, int n_pairs, const int32_t* ref_start, const double* ref_points, const int32_t* tgt_start,
+                     const double* tgt_points, const double* T_init, double* init) {
+  const struct { const int32_t* start; const double* pts; const char *table, *cloud; } sides[2] = {{ref_start, ref_points, "ref_start", "reference"},
+                                                                                                    {tgt_start, tgt_points, "tgt_start", "target"}};
+  for (const auto& side : sides) {
+    const int32_t* start = side.start;
+    const double* pts = side.pts;
+    const auto finite_item = [start, pts](int k) {
+      if (start[k + 1] > start[k] && !pts) return false;
+      for (size_t i = 3 * (size_t)start[k]; i < 3 * (size_t)start[k + 1]; ++i) if (!std::isfinite(pts[i])) return false;
+      return true;
+    };
+    switch (check_start_table(start, n_pairs, INT_MAX, finite_item)) {
+      case kStartNotZero: return refuse_scans(BSGPU_ERR_INVALID, prefix, std::string(side.table) + "[0] must be 0");
+      case kStartDecreasing: return refuse_scans(BSGPU_ERR_INVALID, prefix, std::string(side.table) + " must be non-decreasing");
+      case kStartBadItem: return refuse_scans(BSGPU_ERR_INVALID, prefix, std::string("null or non-finite ") + side.cloud + " points");
+      default: break;
+    }
+  }
+  for (size_t i = 0; i < 12 * (size_t)n_pairs; ++i) {
+    init[i] = T_init ? T_init[i] : kEye[i % 12];
+    if (!std::isfinite(init[i])) return refuse_scans(BSGPU_ERR_INVALID, prefix, "non-finite T_init");
+  }
+  return BSGPU_OK;
+}
+
+// The grids of n_clouds clouds, cloud c under the transform T + 12 c, with cell edge h: the bounding box of every cloud in the frame it
+// is searched in, by the arithmetic the device will use (point_grid.h); the clouds' cells follow one another in the call's cell array.
+// A grid may have BSGPU_ICP_MAX_CELLS cells, the call 16 times as many.  `one`: what the caller's messages call a cloud.
+struct GridsPlan {
+  std::vector<PointGrid> grids;
+  double cells = 0.0;          // of all grids
+  int n_tiles = 0;             // the cell array in scan tiles
+  int max_points = 0;          // the largest cloud
+};
+int plan_grids(const char* prefix, const char* one, size_t n_clouds, const int32_t* start, const double* pts, const double* T, double h, GridsPlan* out) {
+  out->grids.resize(n_clouds);
+  for (size_t c = 0; c < n_clouds; ++c) {
+    const int n = start[c + 1] - start[c];
+    double here;
+    out->max_points = std::max(out->max_points, n);
+    switch (grid_plan(n, pts + 3 * (size_t)start[c], T + 12 * c, h, (int)out->cells, (double)BSGPU_ICP_MAX_CELLS, &out->grids[c], &here)) {
+      case kGridNotFinite: return refuse_scans(BSGPU_ERR_INVALID, prefix, "T_init takes a target point out of range");
+      case kGridTooManyCells: return refuse_scans(BSGPU_ERR_UNSUPPORTED, prefix, std::string("a ") + one + "'s grid exceeds BSGPU_ICP_MAX_CELLS cells");
+      default: break;
+    }
+    out->cells += here;
+    if (out->cells > 16.0 * BSGPU_ICP_MAX_CELLS) return refuse_scans(BSGPU_ERR_UNSUPPORTED, prefix, "the call's grids exceed 16 x BSGPU_ICP_MAX_CELLS cells");
+  }
+  out->n_tiles = (int)(((size_t)out->cells + kGridScanTile - 1) / kGridScanTile);
+  return BSGPU_OK;
+}
+
+// chunk_start (n_pairs + 1): a pair's partial records, one per kGridChunk source points; returns the most chunks of one pair
+int plan_chunks(size_t n_pairs, const int32_t* ref_start, std::vector<int32_t>* chunk_start) {
+  int max_chunks = 0;
+  chunk_start->assign(n_pairs + 1, 0);
+  for (size_t p = 0; p < n_pairs; ++p) {
+    const int chunks = (ref_start[p + 1] - ref_start[p] + kGridChunk - 1) / kGridChunk;
+    (*chunk_start)[p + 1] = (*chunk_start)[p] + chunks;
+    max_chunks = std::max(max_chunks, chunks);
+  }
+  return max_chunks;
+}
 }
 
 extern "C" {
@@ -105,76 +178,27 @@ int bsgpu_register_scans(int device, int32_t n_pairs, const int32_t* ref_start, 
   if (!(t_eps >= 0.0) || !(fit_eps >= 0.0) || !(rel_mse_eps >= 0.0) || rotation_threshold != rotation_threshold)
     return refuse(BSGPU_ERR_INVALID, "register_scans: t_eps, fit_eps and rel_mse_eps must not be negative, no tolerance NaN");
   if (max_iter > BSGPU_ICP_MAX_ITER) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans: max_iter exceeds BSGPU_ICP_MAX_ITER");
-  // the two start tables, in check_start_table's order; an item is bad when one of its points is not finite (a NaN would choose a grid cell)
-  const auto finite_items = [](const int32_t* start, const double* pts) {
-    return [start, pts](int k) {
-      if (start[k + 1] > start[k] && !pts) return false;
-      for (size_t i = 3 * (size_t)start[k]; i < 3 * (size_t)start[k + 1]; ++i) if (!std::isfinite(pts[i])) return false;
-      return true;
-    };
-  };
-  switch (check_start_table(ref_start, n_pairs, INT_MAX, finite_items(ref_start, ref_points))) {
-    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "register_scans: ref_start[0] must be 0");
-    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "register_scans: ref_start must be non-decreasing");
-    case kStartBadItem: return refuse(BSGPU_ERR_INVALID, "register_scans: null or non-finite reference points");
-    default: break;
-  }
-  switch (check_start_table(tgt_start, n_pairs, INT_MAX, finite_items(tgt_start, tgt_points))) {
-    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "register_scans: tgt_start[0] must be 0");
-    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "register_scans: tgt_start must be non-decreasing");
-    case kStartBadItem: return refuse(BSGPU_ERR_INVALID, "register_scans: null or non-finite target points");
-    default: break;
-  }
   const size_t np = (size_t)n_pairs;
-  static const double eye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
   std::vector<double> init(12 * np);
-  for (size_t i = 0; i < init.size(); ++i) {
-    init[i] = T_init ? T_init[i] : eye[i % 12];
-    if (!std::isfinite(init[i])) return refuse(BSGPU_ERR_INVALID, "register_scans: non-finite T_init");
-  }
-  // the grids: the bounding box of every target cloud under its T_init, by the arithmetic the device will use (icp.h)
-  std::vector<IcpGrid> grids(np);
-  std::vector<int32_t> chunk_start(np + 1, 0);
-  double cells = 0.0;
-  int max_targets = 0, max_chunks = 0;
-  for (size_t p = 0; p < np; ++p) {
-    IcpGrid& g = grids[p];
-    g.h = max_corr; g.cell0 = (int)cells;
-    for (int a = 0; a < 3; ++a) { g.o[a] = 0.0; g.n[a] = 0; }
-    const int n = tgt_start[p + 1] - tgt_start[p], chunks = (ref_start[p + 1] - ref_start[p] + kIcpChunk - 1) / kIcpChunk;
-    chunk_start[p + 1] = chunk_start[p] + chunks;
-    max_targets = std::max(max_targets, n); max_chunks = std::max(max_chunks, chunks);
-    if (n == 0) continue;
-    double lo[3], hi[3], q[3];
-    for (int i = 0; i < n; ++i) {
-      icp_apply(&init[12 * p], tgt_points + 3 * ((size_t)tgt_start[p] + i), q);
-      for (int a = 0; a < 3; ++a) { lo[a] = i == 0 || q[a] < lo[a] ? q[a] : lo[a]; hi[a] = i == 0 || q[a] > hi[a] ? q[a] : hi[a]; }
-    }
-    double nc[3], here = 1.0;
-    for (int a = 0; a < 3; ++a) {
-      if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return refuse(BSGPU_ERR_INVALID, "register_scans: T_init takes a target point out of range");
-      nc[a] = icp_axis_cells(lo[a], hi[a], max_corr);
-      here *= nc[a];
-    }
-    if (!(here <= (double)BSGPU_ICP_MAX_CELLS)) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans: a pair's grid exceeds BSGPU_ICP_MAX_CELLS cells");
-    cells += here;
-    if (cells > 16.0 * BSGPU_ICP_MAX_CELLS) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans: the call's grids exceed 16 x BSGPU_ICP_MAX_CELLS cells");
-    for (int a = 0; a < 3; ++a) { g.o[a] = lo[a]; g.n[a] = (int)nc[a]; }
-  }
+  if (const int rc = check_pair_table("register_scans", n_pairs, ref_start, ref_points, tgt_start, tgt_points, T_init, init.data())) return rc;
+  // the grids of the targets under their T_init, cell edge max_corr
+  GridsPlan G;
+  if (const int rc = plan_grids("register_scans", "pair", np, tgt_start, tgt_points, init.data(), max_corr, &G)) return rc;
+  std::vector<int32_t> chunk_start;
+  const int max_chunks = plan_chunks(np, ref_start, &chunk_start);
   if (n_pairs == 0) return BSGPU_OK;
   if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "register_scans: hipSetDevice failed"); }
   const size_t n_ref = (size_t)ref_start[n_pairs], n_tgt = (size_t)tgt_start[n_pairs], n_chunks = (size_t)chunk_start[n_pairs];
-  const int n_tiles = (int)(((size_t)cells + kIcpScanTile - 1) / kIcpScanTile);
   StageLayout L;
   const int s_rs = L.in(ref_start, 4 * (np + 1)), s_ref = L.in(ref_points, 24 * n_ref), s_ts = L.in(tgt_start, 4 * (np + 1)),
             s_tgt = L.in(tgt_points, 24 * n_tgt), s_ti = L.in(init.data(), 96 * np), s_cs = L.in(chunk_start.data(), 4 * (np + 1)),
-            s_gr = L.in(grids.data(), sizeof(IcpGrid) * np);
+            s_gr = L.in(G.grids.data(), sizeof(PointGrid) * np);
   const int s_T = L.out(T_refest_ref, 96 * np), s_Trt = L.out(T_ref_tgt, 96 * np), s_mse = L.out(mse, 8 * np), s_nc = L.out(n_corr, 4 * np),
             s_ni = L.out(n_iters, 4 * np), s_st = L.out(status, 4 * np);
-  // the kernels' working arrays (uninitialised: the launch clears the cells, icp_prepare_kernel sets the per-pair words): the transformed targets and their
+  // the kernels' working arrays (uninitialised: the launch clears the cells, icp_init_kernel sets the per-pair words): the transformed targets and their
   // cells, the grids' cells and their tile sums, the sorted records, the partial records, mse_prev and the done words
-  const int s_tq = L.scratch(24 * n_tgt), s_tc = L.scratch(4 * n_tgt), s_cells = L.scratch(4 * (size_t)n_tiles * kIcpScanTile),
-            s_tile = L.scratch(4 * (size_t)n_tiles), s_rec = L.scratch(32 * n_tgt), s_part = L.scratch(8 * kIcpRec * n_chunks),
+  const int s_tq = L.scratch(24 * n_tgt), s_tc = L.scratch(4 * n_tgt), s_cells = L.scratch(4 * (size_t)G.n_tiles * kGridScanTile),
+            s_tile = L.scratch(4 * (size_t)G.n_tiles), s_rec = L.scratch(32 * n_tgt), s_part = L.scratch(8 * kIcpRec * n_chunks),
             s_prev = L.scratch(8 * np), s_done = L.scratch(4 * np);
   DeviceStage D(L);
   if (!D) return refuse(BSGPU_ERR_DEVICE, "register_scans: out of device memory");
@@ -182,8 +206,8 @@ int bsgpu_register_scans(int device, int32_t n_pairs, const int32_t* ref_start, 
   const auto F = [&](int s) { return D.ptr<double>(s); };
   const auto I = [&](int s) { return D.ptr<int>(s); };
   const hipError_t e = D.run(nullptr, [&] {
-    launch_register_scans(nullptr, n_pairs, max_targets, (int)n_tgt, max_chunks, n_tiles, I(s_rs), F(s_ref), I(s_ts), F(s_tgt), F(s_ti), I(s_cs),
-                          D.ptr<IcpGrid>(s_gr), max_corr, P, F(s_T), F(s_Trt), F(s_mse), I(s_nc), I(s_ni), I(s_st), F(s_tq), I(s_tc), I(s_cells),
+    launch_register_scans(nullptr, n_pairs, G.max_points, (int)n_tgt, max_chunks, G.n_tiles, I(s_rs), F(s_ref), I(s_ts), F(s_tgt), F(s_ti), I(s_cs),
+                          D.ptr<PointGrid>(s_gr), max_corr, P, F(s_T), F(s_Trt), F(s_mse), I(s_nc), I(s_ni), I(s_st), F(s_tq), I(s_tc), I(s_cells),
                           I(s_tile), F(s_rec), F(s_part), F(s_prev), I(s_done));
   });
   if (e != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "register_scans: device error"); }
@@ -213,92 +237,42 @@ int bsgpu_register_scans_gicp(int device, int32_t n_pairs, const int32_t* ref_st
   if (max_iter > BSGPU_ICP_MAX_ITER) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans_gicp: max_iter exceeds BSGPU_ICP_MAX_ITER");
   if (max_inner > BSGPU_GICP_MAX_INNER) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans_gicp: max_inner exceeds BSGPU_GICP_MAX_INNER");
   static_assert(BSGPU_GICP_MAX_K == kGicpMaxK && BSGPU_GICP_MAX_INNER == kGicpMaxInner, "the header's caps are gicp.h's");
-  const auto finite_items = [](const int32_t* start, const double* pts) {
-    return [start, pts](int k) {
-      if (start[k + 1] > start[k] && !pts) return false;
-      for (size_t i = 3 * (size_t)start[k]; i < 3 * (size_t)start[k + 1]; ++i) if (!std::isfinite(pts[i])) return false;
-      return true;
-    };
-  };
-  switch (check_start_table(ref_start, n_pairs, INT_MAX, finite_items(ref_start, ref_points))) {
-    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: ref_start[0] must be 0");
-    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: ref_start must be non-decreasing");
-    case kStartBadItem: return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: null or non-finite reference points");
-    default: break;
-  }
-  switch (check_start_table(tgt_start, n_pairs, INT_MAX, finite_items(tgt_start, tgt_points))) {
-    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: tgt_start[0] must be 0");
-    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: tgt_start must be non-decreasing");
-    case kStartBadItem: return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: null or non-finite target points");
-    default: break;
-  }
   const size_t np = (size_t)n_pairs;
+  std::vector<double> T_cloud(24 * np);
+  if (const int rc = check_pair_table("register_scans_gicp", n_pairs, ref_start, ref_points, tgt_start, tgt_points, T_init, T_cloud.data())) return rc;
   const size_t n_ref = (size_t)ref_start[n_pairs], n_tgt = (size_t)tgt_start[n_pairs], n_pts = n_ref + n_tgt;
   if (n_pts > (size_t)INT_MAX) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans_gicp: more than 2^31 - 1 points in one call");
   // the call's clouds as one packed array: the targets of all pairs, then the sources; a source's transform is the identity
-  static const double eye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  std::vector<double> T_cloud(24 * np), pts(3 * n_pts);
-  std::vector<int32_t> cloud_start(2 * np + 1, 0), chunk_start(np + 1, 0);
-  for (size_t i = 0; i < 12 * np; ++i) {
-    T_cloud[i] = T_init ? T_init[i] : eye[i % 12];
-    T_cloud[12 * np + i] = eye[i % 12];
-    if (!std::isfinite(T_cloud[i])) return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: non-finite T_init");
-  }
+  std::vector<double> pts(3 * n_pts);
+  std::vector<int32_t> cloud_start(2 * np + 1, 0);
+  for (size_t i = 0; i < 12 * np; ++i) T_cloud[12 * np + i] = kEye[i % 12];
   if (n_tgt) std::memcpy(pts.data(), tgt_points, 24 * n_tgt);
   if (n_ref) std::memcpy(pts.data() + 3 * n_tgt, ref_points, 24 * n_ref);
+  int n_live = 0;
   for (size_t p = 0; p < np; ++p) {
     cloud_start[p + 1] = tgt_start[p + 1];
     cloud_start[np + p + 1] = (int32_t)n_tgt + ref_start[p + 1];
+    n_live += ref_start[p + 1] - ref_start[p] >= k_neighbors && tgt_start[p + 1] - tgt_start[p] >= k_neighbors ? 1 : 0;
   }
-  // the grids: the bounding box of every cloud in the frame it is searched in, by the arithmetic the device will use (icp.h)
-  std::vector<IcpGrid> grids(2 * np);
-  double cells = 0.0;
-  int max_points = 0, max_chunks = 0, n_live = 0;
-  for (size_t c = 0; c < 2 * np; ++c) {
-    IcpGrid& g = grids[c];
-    g.h = grid_cell; g.cell0 = (int)cells;
-    for (int a = 0; a < 3; ++a) { g.o[a] = 0.0; g.n[a] = 0; }
-    const int n = cloud_start[c + 1] - cloud_start[c];
-    max_points = std::max(max_points, n);
-    if (n == 0) continue;
-    double lo[3], hi[3], q[3];
-    for (int i = 0; i < n; ++i) {
-      icp_apply(&T_cloud[12 * c], &pts[3 * ((size_t)cloud_start[c] + i)], q);
-      for (int a = 0; a < 3; ++a) { lo[a] = i == 0 || q[a] < lo[a] ? q[a] : lo[a]; hi[a] = i == 0 || q[a] > hi[a] ? q[a] : hi[a]; }
-    }
-    double nc[3], here = 1.0;
-    for (int a = 0; a < 3; ++a) {
-      if (!std::isfinite(lo[a]) || !std::isfinite(hi[a])) return refuse(BSGPU_ERR_INVALID, "register_scans_gicp: T_init takes a target point out of range");
-      nc[a] = icp_axis_cells(lo[a], hi[a], grid_cell);
-      here *= nc[a];
-    }
-    if (!(here <= (double)BSGPU_ICP_MAX_CELLS)) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans_gicp: a cloud's grid exceeds BSGPU_ICP_MAX_CELLS cells");
-    cells += here;
-    if (cells > 16.0 * BSGPU_ICP_MAX_CELLS) return refuse(BSGPU_ERR_UNSUPPORTED, "register_scans_gicp: the call's grids exceed 16 x BSGPU_ICP_MAX_CELLS cells");
-    for (int a = 0; a < 3; ++a) { g.o[a] = lo[a]; g.n[a] = (int)nc[a]; }
-  }
-  for (size_t p = 0; p < np; ++p) {
-    const int ns = ref_start[p + 1] - ref_start[p], nt = tgt_start[p + 1] - tgt_start[p], chunks = (ns + kIcpChunk - 1) / kIcpChunk;
-    chunk_start[p + 1] = chunk_start[p] + chunks;
-    max_chunks = std::max(max_chunks, chunks);
-    n_live += ns >= k_neighbors && nt >= k_neighbors ? 1 : 0;
-  }
+  // the grids of every cloud in the frame it is searched in, cell edge grid_cell
+  GridsPlan G;
+  if (const int rc = plan_grids("register_scans_gicp", "cloud", 2 * np, cloud_start.data(), pts.data(), T_cloud.data(), grid_cell, &G)) return rc;
+  std::vector<int32_t> chunk_start;
+  const int max_chunks = plan_chunks(np, ref_start, &chunk_start);
   if (n_pairs == 0) return BSGPU_OK;
   if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "register_scans_gicp: hipSetDevice failed"); }
   const size_t n_chunks = (size_t)chunk_start[n_pairs];
-  const int n_tiles = (int)(((size_t)cells + kIcpScanTile - 1) / kIcpScanTile);
   StageLayout L;
   const int s_cs = L.in(cloud_start.data(), 4 * (2 * np + 1)), s_pts = L.in(pts.data(), 24 * n_pts), s_tc = L.in(T_cloud.data(), 192 * np),
-            s_ch = L.in(chunk_start.data(), 4 * (np + 1)), s_gr = L.in(grids.data(), sizeof(IcpGrid) * 2 * np);
+            s_ch = L.in(chunk_start.data(), 4 * (np + 1)), s_gr = L.in(G.grids.data(), sizeof(PointGrid) * 2 * np);
   const int s_T = L.out(T_refest_ref, 96 * np), s_Trt = L.out(T_ref_tgt, 96 * np), s_cost = L.out(cost, 8 * np), s_nc = L.out(n_corr, 4 * np),
             s_ni = L.out(n_iters, 4 * np), s_nn = L.out(n_inner, 4 * np), s_st = L.out(status, 4 * np),
             s_cov = L.out(nullptr, ref_cov || tgt_cov ? 48 * n_pts : 0);
   // the kernels' working arrays (uninitialised): the grid build's, the covariances when nobody asked for them, the pairs' states and
   // done words, j(i) and M_i per point, the chunks' kept counts and partial records
-  const int s_tq = L.scratch(24 * n_pts), s_cell = L.scratch(4 * n_pts), s_cells = L.scratch(4 * (size_t)n_tiles * kIcpScanTile),
-            s_tile = L.scratch(4 * (size_t)n_tiles), s_rec = L.scratch(32 * n_pts), s_gT = L.scratch(192 * np), s_gp = L.scratch(16 * np),
-            s_gd = L.scratch(8 * np), s_cov2 = L.scratch(ref_cov || tgt_cov ? 0 : 48 * n_pts), s_state = L.scratch(sizeof(GicpState) * np),
-            s_done = L.scratch(4 * np), s_corr = L.scratch(4 * n_pts), s_M = L.scratch(48 * n_pts), s_kept = L.scratch(4 * n_chunks),
+  const int s_tq = L.scratch(24 * n_pts), s_cell = L.scratch(4 * n_pts), s_cells = L.scratch(4 * (size_t)G.n_tiles * kGridScanTile),
+            s_tile = L.scratch(4 * (size_t)G.n_tiles), s_rec = L.scratch(32 * n_pts), s_cov2 = L.scratch(ref_cov || tgt_cov ? 0 : 48 * n_pts),
+            s_state = L.scratch(sizeof(GicpState) * np), s_done = L.scratch(4 * np), s_corr = L.scratch(4 * n_pts), s_M = L.scratch(48 * n_pts), s_kept = L.scratch(4 * n_chunks),
             s_part = L.scratch(8 * kGicpRec * n_chunks);
   DeviceStage D(L);
   if (!D) return refuse(BSGPU_ERR_DEVICE, "register_scans_gicp: out of device memory");
@@ -307,10 +281,10 @@ int bsgpu_register_scans_gicp(int device, int32_t n_pairs, const int32_t* ref_st
   const auto I = [&](int s) { return D.ptr<int>(s); };
   hipError_t le = hipSuccess;
   const hipError_t e = D.run(nullptr, [&] {
-    le = launch_register_scans_gicp(nullptr, n_pairs, n_live, max_points, (int)n_pts, max_chunks, n_tiles, I(s_cs), F(s_pts), F(s_tc), I(s_ch),
-                                    D.ptr<IcpGrid>(s_gr), P, F(s_T), F(s_Trt), F(s_cost), I(s_nc), I(s_ni), I(s_nn), I(s_st),
-                                    F(ref_cov || tgt_cov ? s_cov : s_cov2), F(s_tq), I(s_cell), I(s_cells), I(s_tile), F(s_rec), F(s_gT), F(s_gp),
-                                    I(s_gd), D.ptr<GicpState>(s_state), I(s_done), I(s_corr), F(s_M), I(s_kept), F(s_part));
+    le = launch_register_scans_gicp(nullptr, n_pairs, n_live, G.max_points, (int)n_pts, max_chunks, G.n_tiles, I(s_cs), F(s_pts), F(s_tc), I(s_ch),
+                                    D.ptr<PointGrid>(s_gr), P, F(s_T), F(s_Trt), F(s_cost), I(s_nc), I(s_ni), I(s_nn), I(s_st),
+                                    F(ref_cov || tgt_cov ? s_cov : s_cov2), F(s_tq), I(s_cell), I(s_cells), I(s_tile), F(s_rec),
+                                    D.ptr<GicpState>(s_state), I(s_done), I(s_corr), F(s_M), I(s_kept), F(s_part));
   });
   if (e != hipSuccess || le != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "register_scans_gicp: device error"); }
   L.scatter();

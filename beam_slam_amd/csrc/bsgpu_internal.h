@@ -550,34 +550,35 @@ void launch_inertial_alignment(hipStream_t s, int n_paths, const int* frame_star
                                int bridge_gap, double min_excitation, int apply_scale, double scale_min, double scale_max, double rank_tol,
                                double* gravity, double* bg, double* scale, double* excitation, int* gyro_rank, double* velocity,
                                double* q_out, double* p_out, double* v_out, int* status, int* own, double* fs, double* ps);
+// The dense grids of a batch of clouds (k_point_grid.hip; point_grid.h).  cloud_start (n_clouds + 1), pts 3 per point, T_cloud 12 and
+// grids 1 per cloud.  Out: tq 3 per point (the points under their cloud's transform), rec 4 per point (the sorted records), cells
+// n_tiles x kGridScanTile ints (every cloud's cells, padded to whole tiles: where each cell's records end).  Scratch: tcell 1 per
+// point, tile_sum n_tiles.
+struct PointGrid;
+constexpr int kGridScanTile = 1024;
+void launch_point_grid_build(hipStream_t s, int n_clouds, int max_points, int n_points, int n_tiles, const int* cloud_start, const double* pts,
+                             const double* T_cloud, const PointGrid* grids, double* tq, int* tcell, int* cells, int* tile_sum, double* rec);
 // ICP scan registration (k_icp.hip, bsgpu_register_scans): a pair over many workgroups.  Inputs as the C-ABI's, on the device, plus
-// what the host derives: chunk_start (n_pairs + 1: a pair's partial records, one per kIcpChunk source points), grids (per pair, icp.h).
-// Scratch: tq 3 / tcell 1 per target, cells n_tiles x kIcpScanTile ints (every pair's grid cells, padded to whole tiles),
-// tile_sum n_tiles, rec 4 per target, part kIcpRec per chunk, mse_prev / done 1 per pair.
-struct IcpGrid; struct IcpParams;
-constexpr int kIcpScanTile = 1024;
+// what the host derives: chunk_start (n_pairs + 1: a pair's partial records, one per kGridChunk source points), grids (per pair's
+// target, cell edge max_corr).  Scratch: the grid build's over the targets, part kIcpRec per chunk, mse_prev / done 1 per pair.
+struct IcpParams;
 void launch_register_scans(hipStream_t s, int n_pairs, int max_targets, int n_targets, int max_chunks, int n_tiles, const int* ref_start,
                            const double* ref, const int* tgt_start, const double* tgt, const double* T_init, const int* chunk_start,
-                           const IcpGrid* grids, double max_corr, const IcpParams& P, double* T, double* T_ref_tgt, double* mse, int* n_corr,
+                           const PointGrid* grids, double max_corr, const IcpParams& P, double* T, double* T_ref_tgt, double* mse, int* n_corr,
                            int* n_iters, int* status, double* tq, int* tcell, int* cells, int* tile_sum, double* rec, double* part,
-                           double* mse_prev, int* done);
-// (the grid build alone: launch_register_scans' once-per-call launches, over any clouds; T 12 / mse_prev 1 / done 1 per cloud are set as there)
-void launch_icp_grid_build(hipStream_t s, int n_pairs, int max_targets, int n_targets, int n_tiles, const int* tgt_start, const double* tgt,
-                           const double* T_init, const IcpGrid* grids, double* tq, int* tcell, int* cells, int* tile_sum, double* rec, double* T,
                            double* mse_prev, int* done);
 // Generalized ICP (k_gicp.hip, bsgpu_register_scans_gicp).  The call's 2 n_pairs clouds are one packed array: cloud p < n_pairs is
 // pair p's target, cloud n_pairs + p its source; cloud_start (2 n_pairs + 1), T_cloud (12 per cloud: T_init, the identity for a
-// source), grids (per cloud, cell edge grid_cell), chunk_start (n_pairs + 1, chunks of kIcpChunk source points).  n_live: the pairs
+// source), grids (per cloud, cell edge grid_cell), chunk_start (n_pairs + 1, chunks of kGridChunk source points).  n_live: the pairs
 // whose clouds both have k points (none: no iteration is enqueued).  Outputs as the C-ABI's; cov 6 per point of the packed array.
-// Scratch: the grid build's (tq, tcell, cells, tile_sum, rec per point; gT 12, gprev, gdone per cloud), state / done per pair,
-// corr 1 and M 6 per point, kept 1 and part kGicpRec per chunk.  The host reads `done` once per outer iteration.
+// Scratch: the grid build's over all clouds, state / done per pair, corr 1 and M 6 per point, kept 1 and part kGicpRec per chunk.
+// The host reads `done` once per outer iteration.
 struct GicpParams; struct GicpState;
 hipError_t launch_register_scans_gicp(hipStream_t s, int n_pairs, int n_live, int max_points, int n_points, int max_chunks, int n_tiles,
                                       const int* cloud_start, const double* pts, const double* T_cloud, const int* chunk_start,
-                                      const IcpGrid* grids, const GicpParams& P, double* T, double* T_ref_tgt, double* cost, int* n_corr,
+                                      const PointGrid* grids, const GicpParams& P, double* T, double* T_ref_tgt, double* cost, int* n_corr,
                                       int* n_iters, int* n_inner, int* status, double* cov, double* tq, int* tcell, int* cells, int* tile_sum,
-                                      double* rec, double* gT, double* gprev, int* gdone, GicpState* state, int* done, int* corr, double* M,
-                                      int* kept, double* part);
+                                      double* rec, GicpState* state, int* done, int* corr, double* M, int* kept, double* part);
 // Scan Context place recognition (k_scan_context.hip, bsgpu_scan_context_describe / _match).  Inputs as the C-ABI's, on the device, plus
 // what the host derives: member_agg (a member's aggregate), max_chunks (chunks of kScChunk points of the longest scan a member names),
 // query_set (a query's set), pair_start (n_queries: where a query's (query, candidate) entries begin), R (the refinement radius).

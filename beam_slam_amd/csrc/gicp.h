@@ -2,10 +2,9 @@
 // (config/matchers/gicp.json), as include/bsgpu.h pins it.  libbeam's GicpMatcher and PCL's GeneralizedIterativeClosestPoint are not
 // in the reference checkout: the covariances, the correspondence rule, the objective and the outer criterion are RECALLED, not
 // verified.  PCL minimises the objective with BFGS over (x, y, z, roll, pitch, yaw); this file minimises the same objective with
-// Gauss-Newton steps, so PCL's iterates are NOT reproduced.  Host- and device-compilable in the style of icp.h, whose pieces it reuses
-// (the grid, the (d^2, index) order, the Jacobi rotation, the chunked sums).
+// Gauss-Newton steps, so PCL's iterates are NOT reproduced.  Host- and device-compilable in the style of icp.h, whose Jacobi rotation it
+// reuses; the clouds' grids, both searches and the chunked sums are point_grid.h's.
 //
-//   gicp_knn, gicp_nearest[_part]  the k nearest points of a cloud / the nearest target below max_corr, through shells of grid cells (exact)
 //   gicp_covariance            PCL's computeCovariances for one point from its neighbour list
 //   gicp_mahalanobis           M = (C'^Q_j + R C'^S_i R^T)^-1
 //   gicp_terms                 the 28 sums' terms of one correspondence: 21 of H's upper triangle, 6 of g, 1 of F
@@ -13,12 +12,12 @@
 //   gicp_advance               one Gauss-Newton step of one pair from its sums, the inner and the outer criteria
 //   gicp_register_serial       (host only) one pair on one core, in the kernels' order of addition
 //
-// Bits.  As in icp.h: contraction is off in every body, an fma appears only where it is written (icp_apply), the sums over the
-// correspondences run in chunks of kIcpChunk source points, inside a chunk in the tree of a 64-lane shuffle-down per wave, the waves
-// in order, the chunks in order; the k neighbours of a point are summed in their (d^2, index) order.  No function of this file calls
+// Bits.  As in point_grid.h: contraction is off in every body, an fma appears only where it is written (grid_apply), the sums over
+// the correspondences have its fixed order; the k neighbours of a point are summed in their (d^2, index) order.  No function of this file calls
 // sin, cos or any other library function that is not correctly rounded on both sides.
 #pragma once
 #include "icp.h"
+#include "point_grid.h"
 
 namespace bsg {
 
@@ -46,177 +45,19 @@ struct GicpState {
   int n_corr, n_iters, n_inner, status, stopped_at;
 };
 
-// ---- the shell search ---------------------------------------------------------------------------------------------------------------------
-// The query's cell, clamped into the grid per axis (a query may lie anywhere; a NaN goes to cell 0 and finds nothing).
-BSG_ICP_FN int gicp_clampi(double f, int n) { return !(f > 0.0) ? 0 : (f > (double)(n - 1) ? n - 1 : (int)f); }
-BSG_ICP_FN void gicp_query_cell(const IcpGrid& g, const double* x, int* cx, int* cy, int* cz) {
-  *cx = gicp_clampi(icp_cell_f(x[0], g.o[0], g.h), g.n[0]);
-  *cy = gicp_clampi(icp_cell_f(x[1], g.o[1], g.h), g.n[1]);
-  *cz = gicp_clampi(icp_cell_f(x[2], g.o[2], g.h), g.n[2]);
+// ---- the searches -----------------------------------------------------------------------------------------------------------------------
+// GICP's two searches are point_grid.h's shell searches: the k nearest points of a cloud for a covariance, and the correspondence,
+// the nearest target below max_corr (strict: d^2 < mc2).  q_out, idx_out: the nearest seen, whatever the threshold says.
+BSG_GRID_FN void gicp_knn(const PointGrid& g, const int* cell_end, const double* rec, const double* x, int k, double* ld, double* li, int stride) {
+  grid_knn(g, cell_end, rec, x, k, ld, li, stride);
 }
-// Shell r of cell (cx, cy, cz): the cells at Chebyshev distance exactly r.  Its part in row (cy + dy, cz + dz), as ranges of the
-// sorted records: the whole span cx - r .. cx + r where |dy| == r or |dz| == r (one range: a row is contiguous), else the two cells
-// cx - r and cx + r.  Returns the number of ranges (0 .. 2).
-BSG_ICP_FN int gicp_row_ranges(const IcpGrid& g, const int* cell_end, int cx, int cy, int cz, int r, int dy, int dz, int* b0, int* e0, int* b1,
-                               int* e1) {
-  const int y = cy + dy, z = cz + dz;
-  *b0 = *e0 = *b1 = *e1 = 0;
-  if (y < 0 || y >= g.n[1] || z < 0 || z >= g.n[2]) return 0;
-  const int row = g.cell0 + (z * g.n[1] + y) * g.n[0];
-  const int xl = cx - r, xh = cx + r;
-  if (dy == r || dy == -r || dz == r || dz == -r) {
-    const int c0 = row + (xl < 0 ? 0 : xl), c1 = row + (xh > g.n[0] - 1 ? g.n[0] - 1 : xh);
-    *b0 = c0 > 0 ? cell_end[c0 - 1] : 0; *e0 = cell_end[c1];
-    return 1;
-  }
-  int n = 0;
-  if (xl >= 0) { *b0 = row + xl > 0 ? cell_end[row + xl - 1] : 0; *e0 = cell_end[row + xl]; n = 1; }
-  if (xh <= g.n[0] - 1) {
-    const int b = cell_end[row + xh - 1], e = cell_end[row + xh];      // (xh >= 1 here: r >= 1)
-    if (n == 0) { *b0 = b; *e0 = e; } else { *b1 = b; *e1 = e; }
-    ++n;
-  }
-  return n;
-}
-// A lower bound of the distance from x to every point of the grid: the largest per-axis gap to the box of the cells.  A point of
-// cell index <= m - 1 has floor(fl((q - o) / h)) < m, hence q < o + h m up to a few ulp; the pad covers that and the rounding of the
-// edge itself (the rule of icp_axis_range, with a wider factor for the longer expression).
-BSG_ICP_FN double gicp_pad(double x, double o, double h, int m) {
-  BSG_ICP_EXACT
-  return 16.0 * kIcpEps * (fabs(x) + fabs(o) + h * (double)(m + 1));
-}
-BSG_ICP_FN double gicp_box_bound(const IcpGrid& g, const double* x) {
-  BSG_ICP_EXACT
-  double D = 0.0;
-  for (int a = 0; a < 3; ++a) {
-    const double below = (g.o[a] - x[a]) - gicp_pad(x[a], g.o[a], g.h, 0);
-    const double above = (x[a] - (g.o[a] + g.h * (double)g.n[a])) - gicp_pad(x[a], g.o[a], g.h, g.n[a]);
-    D = below > D ? below : D;
-    D = above > D ? above : D;
-  }
-  return D;
-}
-// A lower bound of the distance from x to every point of a cell outside shells 0 .. r of cell c: such a cell lies at index
-// >= c + r + 1 or <= c - r - 1 on some axis.  +infinity: there is no such cell.  Never negative.
-BSG_ICP_FN double gicp_shell_bound(const IcpGrid& g, const double* x, int cx, int cy, int cz, int r) {
-  BSG_ICP_EXACT
-  double D = std::numeric_limits<double>::infinity();
-  const int c[3] = {cx, cy, cz};
-  for (int a = 0; a < 3; ++a) {
-    const int hi = c[a] + r + 1, lo = c[a] - r;
-    if (hi <= g.n[a] - 1) {
-      const double d = ((g.o[a] + g.h * (double)hi) - x[a]) - gicp_pad(x[a], g.o[a], g.h, hi);
-      D = d < D ? d : D;
-    }
-    if (lo >= 1) {
-      const double d = (x[a] - (g.o[a] + g.h * (double)lo)) - gicp_pad(x[a], g.o[a], g.h, lo);
-      D = d < D ? d : D;
-    }
-  }
-  return D < 0.0 ? 0.0 : D;
-}
-BSG_ICP_FN double gicp_dist2(const double* r, const double* x) {
-  BSG_ICP_EXACT
-  const double dx = r[0] - x[0], dy = r[1] - x[1], dz = r[2] - x[2];
-  return dx * dx + dy * dy + dz * dz;
-}
-
-// The neighbour list of one query: k entries (d^2, index) in ascending lexicographic order, entry j at ld[j * stride], li[j * stride]
-// (the kernel keeps the lists of a workgroup's points interleaved in LDS); +infinity where there is no entry yet.
-BSG_ICP_FN void gicp_list_insert(double* ld, double* li, int stride, int k, double d2, double idx) {
-  if (!icp_better(d2, idx, ld[(k - 1) * stride], li[(k - 1) * stride])) return;
-  int j = k - 1;
-  while (j > 0 && icp_better(d2, idx, ld[(j - 1) * stride], li[(j - 1) * stride])) {
-    ld[j * stride] = ld[(j - 1) * stride]; li[j * stride] = li[(j - 1) * stride];
-    --j;
-  }
-  ld[j * stride] = d2; li[j * stride] = idx;
-}
-// The k nearest records of x by (d^2, index), no radius.  Shells of cells around x's cell are searched until the k-th best d^2 is
-// below the squared bound of everything not yet searched: every record that could enter the list has then been seen, so the list is
-// brute force's, whatever the cell edge.  Fewer than k records: the tail stays +infinity.
-BSG_ICP_FN void gicp_knn(const IcpGrid& g, const int* cell_end, const double* rec, const double* x, int k, double* ld, double* li, int stride) {
-  BSG_ICP_EXACT
-  const double inf = std::numeric_limits<double>::infinity();
-  for (int j = 0; j < k; ++j) { ld[j * stride] = inf; li[j * stride] = inf; }
-  if (g.n[0] <= 0 || g.n[1] <= 0 || g.n[2] <= 0) return;
-  int cx, cy, cz;
-  gicp_query_cell(g, x, &cx, &cy, &cz);
-  const double box = gicp_box_bound(g, x);
-  for (int r = 0;; ++r) {
-    const int z0 = -r < -cz ? -cz : -r, z1 = r > g.n[2] - 1 - cz ? g.n[2] - 1 - cz : r;
-    const int y0 = -r < -cy ? -cy : -r, y1 = r > g.n[1] - 1 - cy ? g.n[1] - 1 - cy : r;
-    for (int dz = z0; dz <= z1; ++dz) {
-      for (int dy = y0; dy <= y1; ++dy) {
-        int b0, e0, b1, e1;
-        const int nr = gicp_row_ranges(g, cell_end, cx, cy, cz, r, dy, dz, &b0, &e0, &b1, &e1);
-        for (int w = 0; w < nr; ++w) {
-          const int b = w == 0 ? b0 : b1, e = w == 0 ? e0 : e1;
-          for (int p = b; p < e; ++p) {
-            const double* q = rec + 4 * (size_t)p;
-            gicp_list_insert(ld, li, stride, k, gicp_dist2(q, x), q[3]);
-          }
-        }
-      }
-    }
-    const double shell = gicp_shell_bound(g, x, cx, cy, cz, r);
-    if (shell == inf) break;
-    const double D = shell > box ? shell : box;
-    if (ld[(k - 1) * stride] < D * D) break;
-  }
-}
-// The nearest record of x by (d^2, index) among those with d^2 < mc2 (strict).  As gicp_knn with k = 1; the search also ends when
-// nothing not yet searched can lie below the threshold.  false: none (q_out, idx_out then hold the nearest seen, or nothing).
-// gicp_nearest_part is the search of one of nsub lanes that share the query (the kernel's kIcpSub neighbouring lanes, as in
-// icp_correspond_kernel): it visits every nsub-th record of each range from the sub-th on, and after every shell `merge` leaves the
-// best of all the lanes in each of them, so that they all take the same decision to go on.  (d^2, index) is a total order: the merged
-// best does not depend on how the records were dealt out.
-struct GicpNoMerge {
-  BSG_ICP_FN void operator()(double*, double*, double*, double*, double*) const {}
-};
-template <class Merge>
-BSG_ICP_FN bool gicp_nearest_part(const IcpGrid& g, const int* cell_end, const double* rec, const double* x, double mc2, int sub, int nsub,
-                                  Merge merge, double* d2_out, double* q_out, double* idx_out) {
-  BSG_ICP_EXACT
-  const double inf = std::numeric_limits<double>::infinity();
-  double best = inf, bidx = inf, bx = 0.0, by = 0.0, bz = 0.0;
-  if (g.n[0] > 0 && g.n[1] > 0 && g.n[2] > 0) {
-    int cx, cy, cz;
-    gicp_query_cell(g, x, &cx, &cy, &cz);
-    const double box = gicp_box_bound(g, x);
-    for (int r = 0; box * box < mc2; ++r) {
-      const int z0 = -r < -cz ? -cz : -r, z1 = r > g.n[2] - 1 - cz ? g.n[2] - 1 - cz : r;
-      const int y0 = -r < -cy ? -cy : -r, y1 = r > g.n[1] - 1 - cy ? g.n[1] - 1 - cy : r;
-      for (int dz = z0; dz <= z1; ++dz) {
-        for (int dy = y0; dy <= y1; ++dy) {
-          int b0, e0, b1, e1;
-          const int nr = gicp_row_ranges(g, cell_end, cx, cy, cz, r, dy, dz, &b0, &e0, &b1, &e1);
-          for (int w = 0; w < nr; ++w) {
-            const int b = w == 0 ? b0 : b1, e = w == 0 ? e0 : e1;
-            for (int p = b + sub; p < e; p += nsub) {
-              const double* q = rec + 4 * (size_t)p;
-              const double d2 = gicp_dist2(q, x);
-              const bool better = icp_better(d2, q[3], best, bidx);
-              best = better ? d2 : best; bidx = better ? q[3] : bidx;
-              bx = better ? q[0] : bx; by = better ? q[1] : by; bz = better ? q[2] : bz;
-            }
-          }
-        }
-      }
-      merge(&best, &bidx, &bx, &by, &bz);
-      const double shell = gicp_shell_bound(g, x, cx, cy, cz, r);
-      if (shell == inf) break;
-      const double D = shell > box ? shell : box;
-      if (best < D * D || !(D * D < mc2)) break;
-    }
-  }
-  *d2_out = best; *idx_out = bidx;
-  q_out[0] = bx; q_out[1] = by; q_out[2] = bz;
-  return best < mc2;
-}
-BSG_ICP_FN bool gicp_nearest(const IcpGrid& g, const int* cell_end, const double* rec, const double* x, double mc2, double* d2_out, double* q_out,
-                             double* idx_out) {
-  return gicp_nearest_part(g, cell_end, rec, x, mc2, 0, 1, GicpNoMerge(), d2_out, q_out, idx_out);
+BSG_GRID_FN bool gicp_nearest(const PointGrid& g, const int* cell_end, const double* rec, const double* x, double mc2, double* d2_out, double* q_out,
+                              double* idx_out) {
+  GridBest m;
+  const bool kept = grid_shell_nearest(g, cell_end, rec, x, mc2, &m);
+  *d2_out = m.d2; *idx_out = m.idx;
+  q_out[0] = m.x; q_out[1] = m.y; q_out[2] = m.z;
+  return kept;
 }
 
 // ---- covariances ----------------------------------------------------------------------------------------------------------------------------
@@ -224,8 +65,8 @@ BSG_ICP_FN bool gicp_nearest(const IcpGrid& g, const int* cell_end, const double
 // eigenvectors by Jacobi rotations (icp.h's rotation on the symmetric matrix: the columns of C V become orthogonal, their norms are
 // the eigenvalues, V's columns the eigenvectors), eigenvalues in falling order, C' = u1 u1^T + u2 u2^T + epsilon u3 u3^T.
 // c6: xx, xy, xz, yy, yz, zz.  A covariance without a direction (all neighbours equal) leaves V = I: C' = diag(1, 1, epsilon).
-BSG_ICP_FN void gicp_covariance(const double* pts, const double* li, int stride, int k, double epsilon, double* c6) {
-  BSG_ICP_EXACT
+BSG_GRID_FN void gicp_covariance(const double* pts, const double* li, int stride, int k, double epsilon, double* c6) {
+  BSG_GRID_EXACT
   double mx = 0.0, my = 0.0, mz = 0.0;
   for (int j = 0; j < k; ++j) {
     const double* p = pts + 3 * (size_t)li[j * stride];
@@ -258,8 +99,8 @@ BSG_ICP_FN void gicp_covariance(const double* pts, const double* li, int stride,
 
 // M = (C'^Q + R C'^S R^T)^-1, R the rotation block of T (row-major 3 x 4); the inverse of the symmetric positive definite sum by
 // its cofactors.  All three as xx, xy, xz, yy, yz, zz.
-BSG_ICP_FN void gicp_mahalanobis(const double* T, const double* cs, const double* cq, double* m6) {
-  BSG_ICP_EXACT
+BSG_GRID_FN void gicp_mahalanobis(const double* T, const double* cs, const double* cq, double* m6) {
+  BSG_GRID_EXACT
   const double C[3][3] = {{cs[0], cs[1], cs[2]}, {cs[1], cs[3], cs[4]}, {cs[2], cs[4], cs[5]}};
   double P[3][3];
   for (int i = 0; i < 3; ++i)
@@ -279,8 +120,8 @@ BSG_ICP_FN void gicp_mahalanobis(const double* T, const double* cs, const double
 // ---- the sums' terms ------------------------------------------------------------------------------------------------------------------------
 // One correspondence under T: s = T S_i, r = s - q, J = [-[s]x | I] (column k of -[s]x is e_k x s).  H = J^T M J (upper triangle,
 // row-major), g = J^T M r, F = r^T M r; zeros when the point has no correspondence.
-BSG_ICP_FN void gicp_terms(bool kept, const double* s, const double* q, const double* m6, double* t) {
-  BSG_ICP_EXACT
+BSG_GRID_FN void gicp_terms(bool kept, const double* s, const double* q, const double* m6, double* t) {
+  BSG_GRID_EXACT
   const double M[3][3] = {{m6[0], m6[1], m6[2]}, {m6[1], m6[3], m6[4]}, {m6[2], m6[4], m6[5]}};
   const double A[3][3] = {{0.0, -s[2], s[1]}, {s[2], 0.0, -s[0]}, {-s[1], s[0], 0.0}};      // A[k]: e_k x s
   const double r[3] = {s[0] - q[0], s[1] - q[1], s[2] - q[2]};
@@ -304,8 +145,8 @@ BSG_ICP_FN void gicp_terms(bool kept, const double* s, const double* q, const do
 
 // ---- the step -------------------------------------------------------------------------------------------------------------------------------
 // xi = -H^-1 g by a Cholesky factorisation of the summed H.  false: a pivot <= kGicpPivot x its diagonal entry of H (or not a number).
-BSG_ICP_FN bool gicp_solve(const double* sum, double* xi) {
-  BSG_ICP_EXACT
+BSG_GRID_FN bool gicp_solve(const double* sum, double* xi) {
+  BSG_GRID_EXACT
   double H[6][6], L[6][6], y[6];
   int at = 0;
   for (int i = 0; i < 6; ++i)
@@ -338,8 +179,8 @@ BSG_ICP_FN bool gicp_solve(const double* sum, double* xi) {
 }
 // R = exp([w]x) by Rodrigues' formula, R = I + A [w]x + B [w]x^2 with A = sin(th) / th and B = (1 - cos th) / th^2 from their series
 // in th^2 (ten terms: below 2^-60 of the sum at th <= 1/2); a longer w is halved until th <= 1/2 and the rotation squared as often.
-BSG_ICP_FN void gicp_exp(const double* w_in, double* R) {
-  BSG_ICP_EXACT
+BSG_GRID_FN void gicp_exp(const double* w_in, double* R) {
+  BSG_GRID_EXACT
   double w[3] = {w_in[0], w_in[1], w_in[2]};
   double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
   int halvings = 0;
@@ -365,8 +206,8 @@ BSG_ICP_FN void gicp_exp(const double* w_in, double* R) {
   }
 }
 // T <- [exp(w) | v] T, xi = (w, v)
-BSG_ICP_FN void gicp_update(const double* xi, double* T) {
-  BSG_ICP_EXACT
+BSG_GRID_FN void gicp_update(const double* xi, double* T) {
+  BSG_GRID_EXACT
   double R[9], Tn[12];
   gicp_exp(xi, R);
   for (int i = 0; i < 3; ++i) {
@@ -376,8 +217,8 @@ BSG_ICP_FN void gicp_update(const double* xi, double* T) {
   for (int i = 0; i < 12; ++i) T[i] = Tn[i];
 }
 // PCL's outer rule (recalled): delta = max(max |R - R0| / r_eps, max |t - t0| / t_eps); k >= max_iter first, then delta < 1
-BSG_ICP_FN int gicp_outer_status(const double* T0, const double* T, int k, const GicpParams& P) {
-  BSG_ICP_EXACT
+BSG_GRID_FN int gicp_outer_status(const double* T0, const double* T, int k, const GicpParams& P) {
+  BSG_GRID_EXACT
   double delta = 0.0;
   for (int i = 0; i < 3; ++i) {
     for (int j = 0; j < 3; ++j) {
@@ -391,7 +232,7 @@ BSG_ICP_FN int gicp_outer_status(const double* T0, const double* T, int k, const
   return delta < 1.0 ? GICP_TRANSFORM : GICP_NOT_CONVERGED;
 }
 
-BSG_ICP_FN void gicp_state_init(bool enough_points, GicpState* st) {
+BSG_GRID_FN void gicp_state_init(bool enough_points, GicpState* st) {
   for (int i = 0; i < 12; ++i) { st->T[i] = i % 5 == 0 ? 1.0 : 0.0; st->T0[i] = st->T[i]; }
   st->cost = 0.0;
   st->n_corr = 0; st->n_iters = 0; st->n_inner = 0; st->stopped_at = 0;
@@ -400,8 +241,8 @@ BSG_ICP_FN void gicp_state_init(bool enough_points, GicpState* st) {
 // Gauss-Newton step `it` (1-based) of outer iteration k from the 28 sums and the number of kept correspondences.  Fewer than 4 kept:
 // TOO_FEW_CORRESPONDENCES, T stays.  A refused pivot: DEGENERATE, T as before this outer iteration.  Otherwise the step is applied;
 // the inner loop ends after the step whose max |xi| < inner_eps, or after max_inner steps, and the outer criterion is then taken.
-BSG_ICP_FN void gicp_advance(const double* sum, int n_kept, int k, int it, const GicpParams& P, GicpState* st) {
-  BSG_ICP_EXACT
+BSG_GRID_FN void gicp_advance(const double* sum, int n_kept, int k, int it, const GicpParams& P, GicpState* st) {
+  BSG_GRID_EXACT
   if (it == 1) {
     for (int i = 0; i < 12; ++i) st->T0[i] = st->T[i];
     st->n_corr = n_kept;
@@ -427,7 +268,7 @@ BSG_ICP_FN void gicp_advance(const double* sum, int n_kept, int k, int it, const
 
 // ---- one pair on one core (host) ------------------------------------------------------------------------------------------------------------
 // The covariances of one cloud (already in the frame it is searched in) through its grid; cov: 6 per point.
-inline void gicp_cloud_covariances(int n, const double* pts, const IcpSerialGrid& G, int k, double epsilon, double* cov) {
+inline void gicp_cloud_covariances(int n, const double* pts, const SerialGrid& G, int k, double epsilon, double* cov) {
   std::vector<double> ld((size_t)k), li((size_t)k);
   for (int i = 0; i < n; ++i) {
     gicp_knn(G.g, G.cell_end.data(), G.rec.data(), pts + 3 * (size_t)i, k, ld.data(), li.data(), 1);
@@ -440,13 +281,13 @@ inline void gicp_cloud_covariances(int n, const double* pts, const IcpSerialGrid
 inline bool gicp_register_serial(int n_src, const double* S, int n_tgt, const double* Q, const double* T_init, const GicpParams& P,
                                  double grid_cell, double max_cells, double* T, double* T_ref_tgt, double* cost, int* n_corr, int* n_iters,
                                  int* n_inner, int* status, double* ref_cov, double* tgt_cov) {
-  BSG_ICP_EXACT
+  BSG_GRID_EXACT
   static const double eye[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
   const double* Ti = T_init ? T_init : eye;
   std::vector<double> tq(3 * (size_t)n_tgt);
-  for (int i = 0; i < n_tgt; ++i) icp_apply(Ti, Q + 3 * i, &tq[3 * (size_t)i]);
-  IcpSerialGrid GS, GQ;
-  if (!icp_grid_build_serial(n_src, S, grid_cell, max_cells, &GS) || !icp_grid_build_serial(n_tgt, tq.data(), grid_cell, max_cells, &GQ)) return false;
+  for (int i = 0; i < n_tgt; ++i) grid_apply(Ti, Q + 3 * i, &tq[3 * (size_t)i]);
+  SerialGrid GS, GQ;
+  if (!grid_build_serial(n_src, S, grid_cell, max_cells, &GS) || !grid_build_serial(n_tgt, tq.data(), grid_cell, max_cells, &GQ)) return false;
   std::vector<double> cs(6 * (size_t)n_src, 0.0), cq(6 * (size_t)n_tgt, 0.0);
   if (n_src >= P.k) gicp_cloud_covariances(n_src, S, GS, P.k, P.epsilon, cs.data());
   if (n_tgt >= P.k) gicp_cloud_covariances(n_tgt, tq.data(), GQ, P.k, P.epsilon, cq.data());
@@ -455,14 +296,13 @@ inline bool gicp_register_serial(int n_src, const double* S, int n_tgt, const do
   GicpState st;
   gicp_state_init(n_src >= P.k && n_tgt >= P.k, &st);
   const double mc2 = P.max_corr * P.max_corr;
-  const int n_chunks = (n_src + kIcpChunk - 1) / kIcpChunk;
-  std::vector<double> lanes((size_t)kIcpChunk * kGicpRec), M(6 * (size_t)n_src);
+  std::vector<double> M(6 * (size_t)n_src);
   std::vector<int> corr((size_t)n_src);
   for (int k = 1; st.status == GICP_NOT_CONVERGED; ++k) {
     int kept = 0;
     for (int i = 0; i < n_src; ++i) {
       double s[3], q[3], d2, idx;
-      icp_apply(st.T, S + 3 * (size_t)i, s);
+      grid_apply(st.T, S + 3 * (size_t)i, s);
       const bool keep = gicp_nearest(GQ.g, GQ.cell_end.data(), GQ.rec.data(), s, mc2, &d2, q, &idx);
       corr[i] = keep ? (int)idx : -1;
       kept += keep ? 1 : 0;
@@ -471,25 +311,12 @@ inline bool gicp_register_serial(int n_src, const double* S, int n_tgt, const do
     }
     for (int it = 1; st.status == GICP_NOT_CONVERGED && st.stopped_at != k; ++it) {
       double sum[kGicpRec];
-      for (int t = 0; t < kGicpRec; ++t) sum[t] = 0.0;
-      for (int c = 0; c < n_chunks; ++c) {
-        for (int l = 0; l < kIcpChunk; ++l) {
-          double* r = &lanes[(size_t)l * kGicpRec];
-          const int i = c * kIcpChunk + l;
-          if (i < n_src && corr[i] >= 0) {
-            double s[3];
-            icp_apply(st.T, S + 3 * (size_t)i, s);
-            gicp_terms(true, s, &tq[3 * (size_t)corr[i]], &M[6 * (size_t)i], r);
-          } else {
-            for (int t = 0; t < kGicpRec; ++t) r[t] = 0.0;
-          }
-        }
-        for (int t = 0; t < kGicpRec; ++t) {
-          double part = 0.0;
-          for (int w = 0; w < kIcpChunk / kIcpWave; ++w) part = part + icp_wave_tree(&lanes[(size_t)w * kIcpWave * kGicpRec + t], kGicpRec);
-          sum[t] = sum[t] + part;
-        }
-      }
+      grid_chunked_sums<kGicpRec>(n_src, [&](int i, double* r) {
+        if (corr[i] < 0) { for (int t = 0; t < kGicpRec; ++t) r[t] = 0.0; return; }
+        double s[3];
+        grid_apply(st.T, S + 3 * (size_t)i, s);
+        gicp_terms(true, s, &tq[3 * (size_t)corr[i]], &M[6 * (size_t)i], r);
+      }, sum);
       gicp_advance(sum, kept, k, it, P, &st);
     }
   }

@@ -2,8 +2,8 @@
 // RelocCandidateSearchScanContext::AlignSubmapsFromScanMatches (bs_models/src/lib/reloc/reloc_candidate_search_scan_context.cpp:210-262)
 // in its shipped GICP configuration.  The arithmetic of one pair is gicp.h, shared with the CPU tests.
 // A call has few pairs of large clouds (two aggregates of 21 revolutions: 10^5 points each), so a pair is spread over many workgroups:
-//   once per call         launch_icp_grid_build    (k_icp.hip) the counting-sort grid of every cloud of the call: the targets under
-//                                                  T_init, then the sources
+//   once per call         launch_point_grid_build  (k_point_grid.hip) the counting-sort grid of every cloud of the call: the targets
+//                                                  under T_init, then the sources
 //                         gicp_init_kernel         a pair's state: T = I; a cloud of fewer than k points ends it at once
 //                         gicp_covariance_kernel   every point of every cloud: its k nearest (list in LDS), C'
 //   per outer iteration   gicp_correspond_kernel   grid (chunk, pair): per source point j(i) and M_i stored, the chunk's kept count
@@ -13,13 +13,13 @@
 // The workgroups of a pair that is done, or whose inner loop has stopped in this outer iteration, return at once.  The host reads the
 // pairs' done words once per outer iteration (one small copy) and enqueues nothing for an outer iteration that no pair needs.  No
 // workgroup waits for another inside a launch: no fences, no spinning.  No floating-point atomics: the sums have a fixed order
-// (gicp.h), so a pair's bits depend neither on the other pairs of the call nor on the launch geometry.
+// (point_grid.h), so a pair's bits depend neither on the other pairs of the call nor on the launch geometry.
 // The neighbour list of a point is indexed at run time, so it lives in LDS (entry j of thread t at [j * threads + t]: conflict-free),
-// one lane per point; the correspondence search gives a point to kIcpSub lanes.  Both searches are the header's own functions.
+// one lane per point; the correspondence search gives a point to kGridSub lanes.  Both searches are point_grid.h's own functions.
 #include <vector>
 
-#include "bsgpu_device.h"
 #include "gicp.h"
+#include "k_point_grid.h"
 
 namespace bsg {
 
@@ -36,7 +36,7 @@ __global__ __launch_bounds__(64) void gicp_init_kernel(int n_pairs, int k, const
 }
 
 // grid (blocks of kGicpCovThreads points, cloud).  A cloud of fewer than k points has no covariances: zeros.
-__global__ __launch_bounds__(kGicpCovThreads) void gicp_covariance_kernel(const int* cloud_start, const IcpGrid* grids, const int* cells,
+__global__ __launch_bounds__(kGicpCovThreads) void gicp_covariance_kernel(const int* cloud_start, const PointGrid* grids, const int* cells,
                                                                           const double* rec, const double* tq, int k, double epsilon,
                                                                           double* cov) {
   extern __shared__ double gicp_lists[];       // [2][k][kGicpCovThreads]: d^2, index
@@ -54,44 +54,30 @@ __global__ __launch_bounds__(kGicpCovThreads) void gicp_covariance_kernel(const 
   for (int t = 0; t < 6; ++t) cov[6 * (size_t)(first + i) + t] = c6[t];
 }
 
-// the bests of the kIcpSub neighbouring lanes that share a source point, merged by (d^2, index) through three shuffles: every lane of
-// the group ends with the group's best
-struct GicpSubMerge {
-  __device__ void operator()(double* best, double* bidx, double* bx, double* by, double* bz) const {
-#pragma unroll
-    for (int m = 1; m < kIcpSub; m <<= 1) {
-      const double ob = __shfl_xor(*best, m, kIcpWave), oi = __shfl_xor(*bidx, m, kIcpWave);
-      const double ox = __shfl_xor(*bx, m, kIcpWave), oy = __shfl_xor(*by, m, kIcpWave), oz = __shfl_xor(*bz, m, kIcpWave);
-      const bool better = icp_better(ob, oi, *best, *bidx);
-      *best = better ? ob : *best; *bidx = better ? oi : *bidx;
-      *bx = better ? ox : *bx; *by = better ? oy : *by; *bz = better ? oz : *bz;
-    }
-  }
-};
-
-// kIcpSub neighbouring lanes share a source point, as in icp_correspond_kernel: each visits every kIcpSub-th record of a shell's
+// kGridSub neighbouring lanes share a source point, as in icp_correspond_kernel: each visits every kGridSub-th record of a shell's
 // ranges, their bests are merged after every shell (the lanes of a point take every decision of the search together), and the
 // point's first lane forms M and stores.
-__global__ __launch_bounds__(kIcpChunk * kIcpSub) void gicp_correspond_kernel(int n_pairs, const int* cloud_start, const int* chunk_start,
-                                                                    const IcpGrid* grids, const int* cells, const double* rec, const double* tq,
+__global__ __launch_bounds__(kGridChunk * kGridSub) void gicp_correspond_kernel(int n_pairs, const int* cloud_start, const int* chunk_start,
+                                                                    const PointGrid* grids, const int* cells, const double* rec, const double* tq,
                                                                     const double* cov, const GicpState* state, const int* done, double mc2,
                                                                     int* corr, double* M, int* kept_part) {
   const int p = (int)blockIdx.y;
   const int c0 = chunk_start[p];
   if (done[p] != 0 || (int)blockIdx.x >= chunk_start[p + 1] - c0) return;
   const int sfirst = cloud_start[n_pairs + p], n = cloud_start[n_pairs + p + 1] - sfirst, qfirst = cloud_start[p];
-  const int point = (int)threadIdx.x / kIcpSub, sub = (int)threadIdx.x % kIcpSub, i = (int)blockIdx.x * kIcpChunk + point;
+  const int point = (int)threadIdx.x / kGridSub, sub = (int)threadIdx.x % kGridSub, i = (int)blockIdx.x * kGridChunk + point;
   bool kept = false;
   if (i < n) {
-    double T[12], s[3], q[3], d2, idx;
+    double T[12], s[3];
+    GridBest m;
 #pragma unroll
     for (int t = 0; t < 12; ++t) T[t] = state[p].T[t];
     const size_t at = (size_t)(sfirst + i);
-    icp_apply(T, tq + 3 * at, s);
-    kept = gicp_nearest_part(grids[p], cells, rec, s, mc2, sub, kIcpSub, GicpSubMerge(), &d2, q, &idx) && sub == 0;
+    grid_apply(T, tq + 3 * at, s);
+    kept = grid_shell_nearest_part(grids[p], cells, rec, s, mc2, sub, kGridSub, GridSubMerge(), &m) && sub == 0;
     if (sub == 0) {
       double m6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      const int j = kept ? (int)idx : -1;
+      const int j = kept ? (int)m.idx : -1;
       if (kept) gicp_mahalanobis(T, cov + 6 * at, cov + 6 * (size_t)(qfirst + j), m6);
       corr[at] = j;
 #pragma unroll
@@ -102,14 +88,13 @@ __global__ __launch_bounds__(kIcpChunk * kIcpSub) void gicp_correspond_kernel(in
   if (threadIdx.x == 0) kept_part[c0 + (int)blockIdx.x] = count;
 }
 
-__global__ __launch_bounds__(kIcpChunk) void gicp_sums_kernel(int k, int n_pairs, const int* cloud_start, const int* chunk_start, const double* tq,
+__global__ __launch_bounds__(kGridChunk) void gicp_sums_kernel(int k, int n_pairs, const int* cloud_start, const int* chunk_start, const double* tq,
                                                               const GicpState* state, const int* corr, const double* M, double* part) {
-  __shared__ double wave_sum[kIcpChunk / kIcpWave][kGicpRec];
   const int p = (int)blockIdx.y;
   const int c0 = chunk_start[p];
   if (state[p].status != GICP_NOT_CONVERGED || state[p].stopped_at == k || (int)blockIdx.x >= chunk_start[p + 1] - c0) return;
   const int sfirst = cloud_start[n_pairs + p], n = cloud_start[n_pairs + p + 1] - sfirst, qfirst = cloud_start[p];
-  const int i = (int)blockIdx.x * kIcpChunk + (int)threadIdx.x;
+  const int i = (int)blockIdx.x * kGridChunk + (int)threadIdx.x;
   double r[kGicpRec];
 #pragma unroll
   for (int t = 0; t < kGicpRec; ++t) r[t] = 0.0;
@@ -122,26 +107,11 @@ __global__ __launch_bounds__(kIcpChunk) void gicp_sums_kernel(int k, int n_pairs
       for (int t = 0; t < 12; ++t) T[t] = state[p].T[t];
 #pragma unroll
       for (int t = 0; t < 6; ++t) m6[t] = M[6 * at + t];
-      icp_apply(T, tq + 3 * at, s);
+      grid_apply(T, tq + 3 * at, s);
       gicp_terms(true, s, tq + 3 * (size_t)(qfirst + j), m6, r);
     }
   }
-  // lane 0 of each wave: the tree of icp_wave_tree over its 64 points
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-#pragma unroll
-  for (int t = 0; t < kGicpRec; ++t) {
-    double v = r[t];
-#pragma unroll
-    for (int off = kIcpWave / 2; off >= 1; off >>= 1) v = v + __shfl_down(v, off, kIcpWave);
-    if (lane == 0) wave_sum[wave][t] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < kGicpRec) {
-    double sum = 0.0;
-#pragma unroll
-    for (int w = 0; w < kIcpChunk / kIcpWave; ++w) sum = sum + wave_sum[w][threadIdx.x];
-    part[(size_t)(c0 + (int)blockIdx.x) * kGicpRec + threadIdx.x] = sum;
-  }
+  grid_chunk_reduce<kGicpRec>(r, part + (size_t)(c0 + (int)blockIdx.x) * kGicpRec);
 }
 
 __global__ __launch_bounds__(64) void gicp_step_kernel(int k, int it, const int* chunk_start, const double* part, const int* kept_part, GicpParams P,
@@ -152,17 +122,7 @@ __global__ __launch_bounds__(64) void gicp_step_kernel(int k, int it, const int*
   if (state[p].status != GICP_NOT_CONVERGED || state[p].stopped_at == k) return;
   const int c0 = chunk_start[p], c1 = chunk_start[p + 1];
   if (threadIdx.x < kGicpRec) {
-    double s = 0.0;
-    int c = c0;
-    for (; c + 8 <= c1; c += 8) {       // eight loads in flight, added in chunk order
-      double v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = part[(size_t)(c + j) * kGicpRec + threadIdx.x];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s = s + v[j];
-    }
-    for (; c < c1; ++c) s = s + part[(size_t)c * kGicpRec + threadIdx.x];
-    sum[threadIdx.x] = s;
+    sum[threadIdx.x] = grid_sum_partials<kGicpRec>(part, c0, c1);
   } else if (threadIdx.x == kGicpRec) {
     int n = 0;
     for (int c = c0; c < c1; ++c) n += kept_part[c];
@@ -196,14 +156,12 @@ __global__ __launch_bounds__(64) void gicp_finish_kernel(int n_pairs, const Gicp
 
 hipError_t launch_register_scans_gicp(hipStream_t s, int n_pairs, int n_live, int max_points, int n_points, int max_chunks, int n_tiles,
                                       const int* cloud_start, const double* pts, const double* T_cloud, const int* chunk_start,
-                                      const IcpGrid* grids, const GicpParams& P, double* T, double* T_ref_tgt, double* cost, int* n_corr,
+                                      const PointGrid* grids, const GicpParams& P, double* T, double* T_ref_tgt, double* cost, int* n_corr,
                                       int* n_iters, int* n_inner, int* status, double* cov, double* tq, int* tcell, int* cells, int* tile_sum,
-                                      double* rec, double* gT, double* gprev, int* gdone, GicpState* state, int* done, int* corr, double* M,
-                                      int* kept, double* part) {
+                                      double* rec, GicpState* state, int* done, int* corr, double* M, int* kept, double* part) {
   if (n_pairs <= 0) return hipSuccess;
   const int pair_blocks = (n_pairs + 63) / 64;
-  launch_icp_grid_build(s, 2 * n_pairs, max_points, n_points, n_tiles, cloud_start, pts, T_cloud, grids, tq, tcell, cells, tile_sum, rec, gT, gprev,
-                        gdone);
+  launch_point_grid_build(s, 2 * n_pairs, max_points, n_points, n_tiles, cloud_start, pts, T_cloud, grids, tq, tcell, cells, tile_sum, rec);
   hipLaunchKernelGGL(gicp_init_kernel, dim3(pair_blocks), dim3(64), 0, s, n_pairs, P.k, cloud_start, state, done);
   if (max_points > 0)
     hipLaunchKernelGGL(gicp_covariance_kernel, dim3((max_points + kGicpCovThreads - 1) / kGicpCovThreads, 2 * n_pairs), dim3(kGicpCovThreads),
@@ -212,10 +170,10 @@ hipError_t launch_register_scans_gicp(hipStream_t s, int n_pairs, int n_live, in
   const double mc2 = P.max_corr * P.max_corr;
   std::vector<int> done_h((size_t)n_pairs, 0);
   for (int k = 1; k <= P.max_iter && n_live > 0 && max_chunks > 0 && e == hipSuccess; ++k) {
-    hipLaunchKernelGGL(gicp_correspond_kernel, dim3(max_chunks, n_pairs), dim3(kIcpChunk * kIcpSub), 0, s, n_pairs, cloud_start, chunk_start, grids, cells, rec,
+    hipLaunchKernelGGL(gicp_correspond_kernel, dim3(max_chunks, n_pairs), dim3(kGridChunk * kGridSub), 0, s, n_pairs, cloud_start, chunk_start, grids, cells, rec,
                        tq, cov, state, done, mc2, corr, M, kept);
     for (int it = 1; it <= P.max_inner; ++it) {
-      hipLaunchKernelGGL(gicp_sums_kernel, dim3(max_chunks, n_pairs), dim3(kIcpChunk), 0, s, k, n_pairs, cloud_start, chunk_start, tq, state, corr, M,
+      hipLaunchKernelGGL(gicp_sums_kernel, dim3(max_chunks, n_pairs), dim3(kGridChunk), 0, s, k, n_pairs, cloud_start, chunk_start, tq, state, corr, M,
                          part);
       hipLaunchKernelGGL(gicp_step_kernel, dim3(n_pairs), dim3(64), 0, s, k, it, chunk_start, part, kept, P, state, done);
     }

@@ -20,7 +20,7 @@ from test_icp import INC, _compile, comparable, parse_reg, reg_command, run_prog
 
 pytestmark = pytest.mark.gpu
 
-CHUNK = int(re.search(r"constexpr int kIcpChunk = (\d+);", open(os.path.join(INC, "icp.h")).read()).group(1))
+CHUNK = int(re.search(r"constexpr int kGridChunk = (\d+);", open(os.path.join(INC, "point_grid.h")).read()).group(1))
 
 
 @pytest.fixture(scope="module")

@@ -24,7 +24,7 @@ from test_icp import grid_clouds
 
 pytestmark = pytest.mark.gpu
 
-CHUNK = int(re.search(r"constexpr int kIcpChunk = (\d+);", open(os.path.join(INC, "icp.h")).read()).group(1))
+CHUNK = int(re.search(r"constexpr int kGridChunk = (\d+);", open(os.path.join(INC, "point_grid.h")).read()).group(1))
 K = ref.DEFAULTS["k_neighbors"]
 
 
