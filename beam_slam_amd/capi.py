@@ -115,7 +115,7 @@ SYMBOLS = [
     "reprojection_errors", "preintegrate", "triangulate", "time_reproj_jacobian_ms", "reproj_jacobian_bytes", "dense_solve", "plan_info",
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
     "covariance_requests", "localize_frames", "num_factorizations", "essential_ransac", "absolute_pose_ransac",
-    "relative_pose_ransac", "inertial_alignment", "register_scans", "register_scans_error", "register_scans_gicp", "backsub_tangent_table",
+    "relative_pose_ransac", "inertial_alignment", "register_scans", "register_scans_error", "register_scans_gicp", "register_scans_loam", "backsub_tangent_table",
     "scan_context_describe", "scan_context_match", "scan_context_error",
 ]
 
@@ -156,6 +156,18 @@ GICP_DEFAULTS = dict(k_neighbors=10, gicp_epsilon=1e-3, max_corr=5.0, max_iter=1
                      grid_cell=0.5)
 REGISTER_SCANS_GICP_ARGTYPES = [C.c_int, C.c_int32, _ip, _dp, _ip, _dp, _dp, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_double,
                                 C.c_double, C.c_int32, C.c_double, C.c_double, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _dp, _dp]
+#: bsgpu_register_scans_loam: per-pair status values, the limits, the reference's shipped parameters (config/matchers/loam_vlp16.json:
+#: max_correspondence_distance, min_number_measurements, max_correspondence_iterations, the two convergence criteria;
+#: config/optimization/ceres_config.json: HUBER with scaling 1, and under "inner" the solver options it sets over Ceres' defaults;
+#: grid_cell: this library's own, a performance knob that no result depends on) and the typed prototype
+LOAM_MAX_ITERATIONS, LOAM_TRANSFORM, LOAM_TOO_FEW_MEASUREMENTS, LOAM_SOLVER_FAILED = 1, 2, 5, 6
+LOAM_MAX_OUTER, LOAM_MAX_INNER, LOAM_MAX_FEATURES = 100, 1000, 65536
+LOSS_TRIVIAL, LOSS_CAUCHY, LOSS_HUBER = 0, 1, 2
+LOAM_DEFAULTS = dict(max_corr=0.5, min_measurements=30, max_outer=10, conv_translation_m=1e-3, conv_rotation_deg=0.1, loss_kind=LOSS_HUBER,
+                     loss_a=1.0, grid_cell=0.5,
+                     inner=dict(max_num_iterations=50, function_tolerance=1e-8, gradient_tolerance=1e-10, parameter_tolerance=1e-8))
+REGISTER_SCANS_LOAM_ARGTYPES = [C.c_int, C.c_int32, _ip, _dp, _ip, _dp, _ip, _dp, _ip, _dp, _dp, C.c_double, C.c_int32, C.c_int32, C.c_double,
+                                C.c_double, C.POINTER(Options), C.c_int32, C.c_double, C.c_double, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip]
 #: bsgpu_scan_context_describe / bsgpu_scan_context_match: the descriptor's shape, the limits, the reference's shipped parameters
 #: (SCManager's LIDAR_HEIGHT, PC_MAX_RADIUS, NUM_CANDIDATES_FROM_TREE, SEARCH_RATIO, SC_DIST_THRES, recalled) and the typed prototypes
 SC_RINGS, SC_SECTORS, SC_MAX_CANDIDATES, SC_MAX_TREE_CANDIDATES, SC_MAX_SCAN_POINTS = 20, 60, 65536, 64, 65535 * 4096

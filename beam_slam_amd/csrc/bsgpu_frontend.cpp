@@ -1,5 +1,5 @@
 // The front-end entry points of the C-ABI (include/bsgpu.h): bsgpu_preintegrate, bsgpu_inertial_alignment, bsgpu_register_scans,
-// bsgpu_register_scans_gicp, bsgpu_scan_context_describe, bsgpu_scan_context_match, bsgpu_triangulate, bsgpu_localize_frames and the three RANSACs.  Each checks its arguments, describes its arrays as a StageLayout (staging.h:
+// bsgpu_register_scans_gicp, bsgpu_register_scans_loam, bsgpu_scan_context_describe, bsgpu_scan_context_match, bsgpu_triangulate, bsgpu_localize_frames and the three RANSACs.  Each checks its arguments, describes its arrays as a StageLayout (staging.h:
 // [inputs | outputs | scratch] in one device allocation), runs one kernel between one copy in and one copy out, and hands the
 // results to the caller's arrays: nothing is written to them unless the call succeeds.
 #include <algorithm>
@@ -11,6 +11,7 @@
 #include "icp.h"
 #include "point_grid.h"
 #include "inertial_align.h"
+#include "loam.h"
 #include "scan_context.h"
 #include "staging.h"
 
@@ -26,11 +27,13 @@ int refuse_scans(int code, const char* prefix, const std::string& why) { g_regis
 
 // The pair table of a call: the two start tables, in check_start_table's order, an item bad when one of its points is not finite (a
 // NaN would choose a grid cell); init (12 per pair) <- T_init, the identity without one, which must be finite.  BSGPU_OK, or the
-// refusal with its message under the caller's prefix.
+// refusal with its message under the caller's prefix.  names (optional): what the messages call the two tables and the two clouds.
 int check_pair_table(const char* prefix, int n_pairs, const int32_t* ref_start, const double* ref_points, const int32_t* tgt_start,
-                     const double* tgt_points, const double* T_init, double* init) {
-  const struct { const int32_t* start; const double* pts; const char *table, *cloud; } sides[2] = {{ref_start, ref_points, "ref_start", "reference"},
-                                                                                                    {tgt_start, tgt_points, "tgt_start", "target"}};
+                     const double* tgt_points, const double* T_init, double* init, const char* const* names = nullptr) {
+  static const char* const plain[4] = {"ref_start", "reference", "tgt_start", "target"};
+  if (!names) names = plain;
+  const struct { const int32_t* start; const double* pts; const char *table, *cloud; } sides[2] = {{ref_start, ref_points, names[0], names[1]},
+                                                                                                    {tgt_start, tgt_points, names[2], names[3]}};
   for (const auto& side : sides) {
     const int32_t* start = side.start;
     const double* pts = side.pts;
@@ -296,6 +299,106 @@ int bsgpu_register_scans_gicp(int device, int32_t n_pairs, const int32_t* ref_st
   return BSGPU_OK;
 } catch (...) {
   try { g_register_scans_error = "register_scans_gicp: out of host memory"; } catch (...) {}
+  return api_exception(nullptr);
+}
+
+int bsgpu_register_scans_loam(int device, int32_t n_pairs, const int32_t* ref_edge_start, const double* ref_edges, const int32_t* ref_surf_start,
+                              const double* ref_surfs, const int32_t* tgt_edge_start, const double* tgt_edges, const int32_t* tgt_surf_start,
+                              const double* tgt_surfs, const double* T_init, double max_corr, int32_t min_measurements, int32_t max_outer,
+                              double conv_translation_m, double conv_rotation_deg, const bsgpu_options* inner, int32_t loss_kind, double loss_a,
+                              double grid_cell, double* T_refest_ref, double* T_ref_tgt, double* cov, double* cost, int32_t* n_edge,
+                              int32_t* n_surf, int32_t* n_iters, int32_t* n_inner, int32_t* status) try {
+  const char* const me = "register_scans_loam";
+  const auto refuse = [me](int code, const char* why) { return refuse_scans(code, me, why); };
+  if (n_pairs < 0 || !ref_edge_start || !ref_surf_start || !tgt_edge_start || !tgt_surf_start || !inner || !T_refest_ref || !status)
+    return refuse(BSGPU_ERR_INVALID, "null argument");
+  if (!(max_corr > 0.0) || !std::isfinite(max_corr)) return refuse(BSGPU_ERR_INVALID, "max_corr must be positive and finite");
+  if (!(grid_cell > 0.0) || !std::isfinite(grid_cell)) return refuse(BSGPU_ERR_INVALID, "grid_cell must be positive and finite");
+  if (min_measurements < 1) return refuse(BSGPU_ERR_INVALID, "min_measurements must be at least 1");
+  if (max_outer < 1) return refuse(BSGPU_ERR_INVALID, "max_outer must be at least 1");
+  if (!(conv_translation_m >= 0.0) || !(conv_rotation_deg >= 0.0))
+    return refuse(BSGPU_ERR_INVALID, "conv_translation_m and conv_rotation_deg must not be negative or NaN");
+  if (!(conv_rotation_deg < 180.0)) return refuse(BSGPU_ERR_INVALID, "conv_rotation_deg must be below 180");
+  if (loss_kind < BSGPU_LOSS_TRIVIAL || loss_kind > BSGPU_LOSS_HUBER) return refuse(BSGPU_ERR_INVALID, "unknown loss kind");
+  if (loss_kind == BSGPU_LOSS_HUBER && (!(loss_a > 0.0) || !std::isfinite(loss_a)))
+    return refuse(BSGPU_ERR_INVALID, "loss_a must be positive and finite for the Huber loss");
+  if (loss_kind == BSGPU_LOSS_CAUCHY) return refuse(BSGPU_ERR_UNSUPPORTED, "the Cauchy loss is not supported (its logarithm differs between host and device)");
+  if (inner->trust_region_strategy_type != BSGPU_TR_LEVENBERG_MARQUARDT)
+    return refuse(BSGPU_ERR_UNSUPPORTED, "its in-kernel loop is Levenberg-Marquardt only (trust_region_strategy_type must be 0)");
+  if (max_outer > BSGPU_LOAM_MAX_OUTER) return refuse(BSGPU_ERR_UNSUPPORTED, "max_outer exceeds BSGPU_LOAM_MAX_OUTER");
+  if (inner->max_num_iterations > BSGPU_LOAM_MAX_INNER) return refuse(BSGPU_ERR_UNSUPPORTED, "inner->max_num_iterations exceeds BSGPU_LOAM_MAX_INNER");
+  static_assert(BSGPU_LOAM_MAX_OUTER == kLoamMaxOuter && BSGPU_LOAM_MAX_INNER == kLoamMaxInner && BSGPU_LOAM_MAX_FEATURES == kLoamMaxFeatures,
+                "the header's caps are loam.h's");
+  static_assert(BSGPU_LOAM_MAX_ITERATIONS == LOAM_MAX_ITERATIONS && BSGPU_LOAM_TRANSFORM == LOAM_TRANSFORM &&
+                BSGPU_LOAM_TOO_FEW_MEASUREMENTS == LOAM_TOO_FEW_MEASUREMENTS && BSGPU_LOAM_SOLVER_FAILED == LOAM_SOLVER_FAILED, "the header's status values are loam.h's");
+  const size_t np = (size_t)n_pairs;
+  std::vector<double> init(12 * np);
+  static const char* const edge_names[4] = {"ref_edge_start", "reference edge", "tgt_edge_start", "target edge"};
+  static const char* const surf_names[4] = {"ref_surf_start", "reference surface", "tgt_surf_start", "target surface"};
+  if (const int rc = check_pair_table(me, n_pairs, ref_edge_start, ref_edges, tgt_edge_start, tgt_edges, T_init, init.data(), edge_names)) return rc;
+  if (const int rc = check_pair_table(me, n_pairs, ref_surf_start, ref_surfs, tgt_surf_start, tgt_surfs, T_init, init.data(), surf_names)) return rc;
+  const size_t n_re = (size_t)ref_edge_start[n_pairs], n_rs = (size_t)ref_surf_start[n_pairs], n_te = (size_t)tgt_edge_start[n_pairs],
+               n_ts = (size_t)tgt_surf_start[n_pairs], n_ref = n_re + n_rs, n_tgt = n_te + n_ts;
+  if (n_ref > (size_t)INT_MAX || n_tgt > (size_t)INT_MAX) return refuse(BSGPU_ERR_UNSUPPORTED, "more than 2^31 - 1 points in one call");
+  // the call's reference clouds as one packed array, every pair's edges and then every pair's surfaces, each its own cloud with its own
+  // grid (the identity as its transform); the target features packed likewise
+  std::vector<double> ref(3 * n_ref), tgt(3 * n_tgt), T_cloud(24 * np);
+  std::vector<int32_t> cloud_start(2 * np + 1, 0), feat_start(2 * np + 1, 0);
+  if (n_re) std::memcpy(ref.data(), ref_edges, 24 * n_re);
+  if (n_rs) std::memcpy(ref.data() + 3 * n_re, ref_surfs, 24 * n_rs);
+  if (n_te) std::memcpy(tgt.data(), tgt_edges, 24 * n_te);
+  if (n_ts) std::memcpy(tgt.data() + 3 * n_te, tgt_surfs, 24 * n_ts);
+  for (size_t i = 0; i < 24 * np; ++i) T_cloud[i] = kEye[i % 12];
+  for (size_t p = 0; p < np; ++p) {
+    cloud_start[p + 1] = ref_edge_start[p + 1]; cloud_start[np + p + 1] = (int32_t)n_re + ref_surf_start[p + 1];
+    feat_start[p + 1] = tgt_edge_start[p + 1]; feat_start[np + p + 1] = (int32_t)n_te + tgt_surf_start[p + 1];
+    if ((tgt_edge_start[p + 1] - tgt_edge_start[p]) + (size_t)(tgt_surf_start[p + 1] - tgt_surf_start[p]) > (size_t)BSGPU_LOAM_MAX_FEATURES)
+      return refuse(BSGPU_ERR_UNSUPPORTED, "a pair has more than BSGPU_LOAM_MAX_FEATURES target features");
+  }
+  GridsPlan G;
+  if (const int rc = plan_grids(me, "reference cloud", 2 * np, cloud_start.data(), ref.data(), T_cloud.data(), grid_cell, &G)) return rc;
+  if (n_pairs == 0) return BSGPU_OK;
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "hipSetDevice failed"); }
+  LoamParams P;
+  P.mc2 = max_corr * max_corr; P.min_measurements = min_measurements; P.max_outer = max_outer;
+  P.conv_translation = conv_translation_m; P.cos_rotation = loam_cos_bound(conv_rotation_deg);
+  P.loss_kind = loss_kind; P.loss_a = loss_a; P.inner = *inner;
+  StageLayout L;
+  const int s_cs = L.in(cloud_start.data(), 4 * (2 * np + 1)), s_ref = L.in(ref.data(), 24 * n_ref), s_tc = L.in(T_cloud.data(), 192 * np),
+            s_gr = L.in(G.grids.data(), sizeof(PointGrid) * 2 * np), s_fs = L.in(feat_start.data(), 4 * (2 * np + 1)), s_tgt = L.in(tgt.data(), 24 * n_tgt),
+            s_ti = L.in(init.data(), 96 * np);
+  // per-pair records, split below: kLoamOutStride doubles and 5 ints (bsgpu_internal.h)
+  const int s_od = L.out(nullptr, 8 * kLoamOutStride * np), s_oi = L.out(nullptr, 4 * 5 * np);
+  // the kernels' working arrays (uninitialised): the grid build's over the reference clouds, the target features under T_init, the
+  // measurements (three neighbour indices per target feature)
+  const int s_rq = L.scratch(24 * n_ref), s_cell = L.scratch(4 * n_ref), s_cells = L.scratch(4 * (size_t)G.n_tiles * kGridScanTile),
+            s_tile = L.scratch(4 * (size_t)G.n_tiles), s_rec = L.scratch(32 * n_ref), s_tq = L.scratch(24 * n_tgt), s_corr = L.scratch(12 * n_tgt);
+  DeviceStage D(L);
+  if (!D) return refuse(BSGPU_ERR_DEVICE, "out of device memory");
+  const auto F = [&](int s) { return D.ptr<double>(s); };
+  const auto I = [&](int s) { return D.ptr<int>(s); };
+  const hipError_t e = D.run(nullptr, [&] {
+    launch_register_scans_loam(nullptr, n_pairs, G.max_points, (int)n_ref, G.n_tiles, I(s_cs), F(s_ref), F(s_tc), D.ptr<PointGrid>(s_gr), I(s_fs),
+                               F(s_tgt), F(s_ti), P, F(s_od), I(s_oi), F(s_rq), I(s_cell), I(s_cells), I(s_tile), F(s_rec), F(s_tq), I(s_corr));
+  });
+  if (e != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "device error"); }
+  const double* od = L.out_image<double>(s_od);
+  const int32_t* oi = L.out_image<int32_t>(s_oi);
+  for (size_t p = 0; p < np; ++p) {
+    const double* r = od + kLoamOutStride * p;
+    std::memcpy(T_refest_ref + 12 * p, r, 12 * sizeof(double));
+    if (T_ref_tgt) std::memcpy(T_ref_tgt + 12 * p, r + 12, 12 * sizeof(double));
+    if (cov) std::memcpy(cov + 36 * p, r + 24, 36 * sizeof(double));
+    if (cost) cost[p] = r[60];
+    if (n_edge) n_edge[p] = oi[5 * p];
+    if (n_surf) n_surf[p] = oi[5 * p + 1];
+    if (n_iters) n_iters[p] = oi[5 * p + 2];
+    if (n_inner) n_inner[p] = oi[5 * p + 3];
+    status[p] = oi[5 * p + 4];
+  }
+  return BSGPU_OK;
+} catch (...) {
+  try { g_register_scans_error = "register_scans_loam: out of host memory"; } catch (...) {}
   return api_exception(nullptr);
 }
 

@@ -579,6 +579,18 @@ hipError_t launch_register_scans_gicp(hipStream_t s, int n_pairs, int n_live, in
                                       const PointGrid* grids, const GicpParams& P, double* T, double* T_ref_tgt, double* cost, int* n_corr,
                                       int* n_iters, int* n_inner, int* status, double* cov, double* tq, int* tcell, int* cells, int* tile_sum,
                                       double* rec, GicpState* state, int* done, int* corr, double* M, int* kept, double* part);
+// LOAM feature registration (k_loam.hip, bsgpu_register_scans_loam): one workgroup per pair.  The call's 2 n_pairs reference clouds are
+// one packed array (ref): cloud p < n_pairs is pair p's edges, cloud n_pairs + p its surfaces; cloud_start (2 n_pairs + 1), T_cloud (12
+// per cloud: the identity), grids (per cloud, cell edge grid_cell); the target features (tgt) packed likewise under feat_start; T_init 12
+// per pair.  out kLoamOutStride doubles per pair [T_refest_ref 12 | T_ref_tgt 12 | covariance 6x6 of (p, theta) | cost], out_i 5 per
+// pair [n_edge, n_surf, n_iters, n_inner, status].  Scratch: the grid build's over the reference clouds (rq 3 per point), tq 3 and corr
+// 3 per target feature.
+struct LoamParams;
+constexpr int kLoamOutStride = 61;
+void launch_register_scans_loam(hipStream_t s, int n_pairs, int max_points, int n_points, int n_tiles, const int* cloud_start, const double* ref,
+                                const double* T_cloud, const PointGrid* grids, const int* feat_start, const double* tgt, const double* T_init,
+                                const LoamParams& P, double* out, int* out_i, double* rq, int* tcell, int* cells, int* tile_sum, double* rec,
+                                double* tq, int* corr);
 // Scan Context place recognition (k_scan_context.hip, bsgpu_scan_context_describe / _match).  Inputs as the C-ABI's, on the device, plus
 // what the host derives: member_agg (a member's aggregate), max_chunks (chunks of kScChunk points of the longest scan a member names),
 // query_set (a query's set), pair_start (n_queries: where a query's (query, candidate) entries begin), R (the refinement radius).

@@ -63,6 +63,10 @@ BSG_FLM_FN void flm_quat_plus(const double x[4], const double d[3], double out[4
   out[2] = x[0] * b[2] - x[1] * b[3] + x[2] * b[0] + x[3] * b[1];
   out[3] = x[0] * b[3] + x[1] * b[2] - x[2] * b[1] + x[3] * b[0];
 }
+// the Plus of flm_solve and flm_grad_norms unless a caller passes another (loam.h does: one without library sines)
+struct FlmQuatPlus {
+  BSG_FLM_FN void operator()(const double x[4], const double d[3], double out[4]) const { flm_quat_plus(x, d, out); }
+};
 // ceres::LossFunction::Evaluate: rho(s), *rho1 = rho'(s) (bsgpu_device.h loss_eval)
 BSG_FLM_FN double flm_loss(int kind, double a, double s, double* rho1) {
   if (kind == BSGPU_LOSS_CAUCHY) {
@@ -182,10 +186,11 @@ BSG_FLM_FN void flm_chol6_solve(const double L[36], double b[6]) {
   }
 }
 // |x - Plus(x, -g)| over the ambient (q, p): max and sum of squares (SC_GRAD_MAX, SC_GRAD_NORM2)
-BSG_FLM_FN void flm_grad_norms(const double q[4], const double p[3], const double g[6], double* gmax, double* gn2) {
+template <class Plus = FlmQuatPlus>
+BSG_FLM_FN void flm_grad_norms(const double q[4], const double p[3], const double g[6], double* gmax, double* gn2, Plus plus = Plus()) {
   const double ng[3] = {-g[3], -g[4], -g[5]};
   double qm[4];
-  flm_quat_plus(q, ng, qm);
+  plus(q, ng, qm);
   double mx = 0.0, s2 = 0.0;
   for (int i = 0; i < 4; ++i) { const double d = q[i] - qm[i]; s2 += d * d; mx = fmax(mx, fabs(d)); }
   for (int i = 0; i < 3; ++i) { const double d = g[i]; s2 += d * d; mx = fmax(mx, fabs(d)); }
@@ -196,10 +201,11 @@ BSG_FLM_FN void flm_grad_norms(const double q[4], const double p[3], const doubl
 // every caller the same sums.  On return res holds the pose reached, its cost, the iteration count (LmState: the iterations
 // recorded, i.e. not the one a tolerance or the invalid-step limit ends), the status and, for FLM_REFINED, the covariance
 // (J^T J)^-1 of [p, theta] at that pose (NaN otherwise).  trace (optional, max_num_iterations entries): the fate of each recorded
-// iteration, FLM_STEP_*.
+// iteration, FLM_STEP_*.  plus: the orientation's Plus, flm_quat_plus unless the caller needs another.
 enum { FLM_STEP_INVALID = 0, FLM_STEP_REJECTED = 1, FLM_STEP_ACCEPTED = 2 };
-template <class Eval>
-BSG_FLM_FN void flm_solve(const bsgpu_options& o, const double q0[4], const double p0[3], Eval& ev, FlmResult& res, int* trace = nullptr) {
+template <class Eval, class Plus = FlmQuatPlus>
+BSG_FLM_FN void flm_solve(const bsgpu_options& o, const double q0[4], const double p0[3], Eval& ev, FlmResult& res, int* trace = nullptr,
+                          Plus plus = Plus()) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -213,7 +219,7 @@ BSG_FLM_FN void flm_solve(const bsgpu_options& o, const double q0[4], const doub
   bool failed = !std::isfinite(x_cost);
   for (int i = 0; i < 6; ++i) scale[i] = o.jacobi_scaling ? 1.0 / (1.0 + sqrt(H[7 * i])) : 1.0;
   double gmax, gn2;
-  flm_grad_norms(q, p, g, &gmax, &gn2);
+  flm_grad_norms(q, p, g, &gmax, &gn2, plus);
   double x_norm = 0.0;
   for (int i = 0; i < 4; ++i) x_norm += q[i] * q[i];
   for (int i = 0; i < 3; ++i) x_norm += p[i] * p[i];
@@ -262,7 +268,7 @@ BSG_FLM_FN void flm_solve(const bsgpu_options& o, const double q0[4], const doub
     n_invalid = 0;
     double qc[4], pc[3];
     const double dth[3] = {y[3] * scale[3], y[4] * scale[4], y[5] * scale[5]};
-    flm_quat_plus(q, dth, qc);
+    plus(q, dth, qc);
     for (int i = 0; i < 3; ++i) pc[i] = p[i] + y[i] * scale[i];
     ev(qc, pc, false, s);
     double cand_cost = s.v[0];
@@ -280,7 +286,7 @@ BSG_FLM_FN void flm_solve(const bsgpu_options& o, const double q0[4], const doub
       ev(q, p, true, s);
       x_cost = s.v[0];
       flm_unpack(s, H, g);
-      flm_grad_norms(q, p, g, &gmax, &gn2);
+      flm_grad_norms(q, p, g, &gmax, &gn2, plus);
       x_norm = 0.0;
       for (int i = 0; i < 4; ++i) x_norm += q[i] * q[i];
       for (int i = 0; i < 3; ++i) x_norm += p[i] * p[i];

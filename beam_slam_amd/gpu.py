@@ -173,6 +173,57 @@ def register_scans_gicp(ref_start, ref_points, tgt_start, tgt_points, T_init=Non
     return out
 
 
+def loam_options(inner=None):
+    """The inner solve's options: Ceres' defaults (bsgpu_options_default) under the fields of capi.LOAM_DEFAULTS["inner"], then under
+    `inner` (a dict of fields; a capi.Options is taken as it is)."""
+    if isinstance(inner, capi.Options):
+        return inner
+    o = capi.Options()
+    fn = lib().bsgpu_options_default
+    fn.argtypes = [ctypes.POINTER(capi.Options)]
+    fn.restype = None
+    fn(ctypes.byref(o))
+    for k, v in dict(capi.LOAM_DEFAULTS["inner"], **(inner or {})).items():
+        setattr(o, k, v)
+    return o
+
+
+def register_scans_loam(ref_edge_start, ref_edges, ref_surf_start, ref_surfs, tgt_edge_start, tgt_edges, tgt_surf_start, tgt_surfs, T_init=None,
+                        max_corr=capi.LOAM_DEFAULTS["max_corr"], min_measurements=capi.LOAM_DEFAULTS["min_measurements"],
+                        max_outer=capi.LOAM_DEFAULTS["max_outer"], conv_translation_m=capi.LOAM_DEFAULTS["conv_translation_m"],
+                        conv_rotation_deg=capi.LOAM_DEFAULTS["conv_rotation_deg"], inner=None, loss_kind=capi.LOAM_DEFAULTS["loss_kind"],
+                        loss_a=capi.LOAM_DEFAULTS["loss_a"], grid_cell=capi.LOAM_DEFAULTS["grid_cell"], device=0):
+    """bsgpu_register_scans_loam: LOAM registration from feature clouds (the reference's matcher in its shipped LOAM configuration) for a
+    batch of scan pairs.  Pair p moves the target's edge features tgt_edges[tgt_edge_start[p]:tgt_edge_start[p+1]] and surface features
+    (under T_init[p], 3 x 4, first when given) onto the reference's, which are searched.  inner: see loam_options.  Returns a dict of
+    arrays: T_refest_ref and T_ref_tgt (P x 3 x 4), cov (P x 6 x 6, tangent [p, theta]), cost, n_edge, n_surf, n_iters, n_inner, status (P)."""
+    import numpy as np
+    starts = [np.ascontiguousarray(a, np.int32).reshape(-1) for a in (ref_edge_start, ref_surf_start, tgt_edge_start, tgt_surf_start)]
+    clouds = [np.ascontiguousarray(a, np.float64).reshape(-1, 3) for a in (ref_edges, ref_surfs, tgt_edges, tgt_surfs)]
+    P = starts[0].size - 1
+    ti = None if T_init is None else np.ascontiguousarray(T_init, np.float64).reshape(-1, 3, 4)
+    if P < 0 or any(a.size != P + 1 for a in starts) or (ti is not None and ti.shape[0] != P):
+        raise capi.SolverError(capi.ERR_INVALID, "register_scans_loam: array sizes do not agree")
+    if any(int(a.max()) > c.shape[0] for a, c in zip(starts, clouds)):
+        raise capi.SolverError(capi.ERR_INVALID, "register_scans_loam: a start table names more points than were passed")
+    out = dict(T_refest_ref=np.zeros((P, 3, 4)), T_ref_tgt=np.zeros((P, 3, 4)), cov=np.zeros((P, 6, 6)), cost=np.zeros(P),
+               n_edge=np.zeros(P, np.int32), n_surf=np.zeros(P, np.int32), n_iters=np.zeros(P, np.int32), n_inner=np.zeros(P, np.int32),
+               status=np.zeros(P, np.int32))
+    fn = lib().bsgpu_register_scans_loam
+    fn.argtypes = capi.REGISTER_SCANS_LOAM_ARGTYPES
+    _dp, _ip = capi._dp, capi._ip
+    d = lambda x: None if x is None else x.ctypes.data_as(_dp)
+    i = lambda x: x.ctypes.data_as(_ip)
+    opt = loam_options(inner)
+    rc = fn(device, P, i(starts[0]), d(clouds[0]), i(starts[1]), d(clouds[1]), i(starts[2]), d(clouds[2]), i(starts[3]), d(clouds[3]), d(ti),
+            float(max_corr), int(min_measurements), int(max_outer), float(conv_translation_m), float(conv_rotation_deg), ctypes.byref(opt),
+            int(loss_kind), float(loss_a), float(grid_cell), d(out["T_refest_ref"]), d(out["T_ref_tgt"]), d(out["cov"]), d(out["cost"]),
+            i(out["n_edge"]), i(out["n_surf"]), i(out["n_iters"]), i(out["n_inner"]), i(out["status"]))
+    if rc != 0:
+        raise capi.SolverError(rc, register_scans_error())
+    return out
+
+
 def register_scans_error():
     """What this thread's last failed bsgpu_register_scans objected to."""
     fn = lib().bsgpu_register_scans_error

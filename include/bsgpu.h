@@ -629,6 +629,71 @@ int bsgpu_register_scans_gicp(int device, int32_t n_pairs, const int32_t* ref_st
                               double* T_refest_ref, double* T_ref_tgt, double* cost, int32_t* n_corr, int32_t* n_iters, int32_t* n_inner,
                               int32_t* status, double* ref_cov, double* tgt_cov);
 
+/* LOAM feature registration for a batch of scan pairs — the matcher_->Match() of MultiScanLoamRegistration::MatchScans
+ * (bs_models/src/lib/scan_registration/multi_scan_registration.cpp:497-531), ScanToMapLoamRegistration (scan_to_map_registration.cpp:
+ * 158-188), RelocRefinementLoamRegistration (reloc_refinement_loam_registration.cpp:91-118), submap_alignment.cpp:76-96 and
+ * global_map_batch_optimization.cpp:238-247 in the shipped configuration (config/matchers/loam_*.json, optimization/ceres_config.json).
+ * The matcher's boundary is kept: LoamPointCloud in, transform and covariance out; feature extraction (LoamFeatureExtractor) is a
+ * separate step and stays with the caller.  [EXT] libbeam's LoamMatcher, LoamScanRegistration, CeresPointToLineCostFunction and
+ * CeresPointToPlaneCostFunction are not in the reference checkout: everything below is RECALLED, not verified, and where the text says
+ * "the library's choice" this library decides something the recollection leaves open.
+ *   clouds            pair p has four packed-xyz clouds, start tables as in bsgpu_register_scans: the reference's edge and surface
+ *                     features and the target's.  They are the STRONG features of a LoamPointCloud (edges.strong, surfaces.strong):
+ *                     every shipped matcher file sets ignore_weak_features and check_strong_features_first.  NOT MODELLED: weak
+ *                     features as a second search tier, validate_correspondences, the matcher's max_solver_time_in_seconds.  A caller
+ *                     who wants weak features matched passes them concatenated to the strong ones.  T_init (optional, 12 doubles per
+ *                     pair, row-major 3 x 4; NULL: the identity) is applied to the target features on the device first.
+ *   roles             the reverse of ICP: the reference clouds are searched, the target features are the queries, and it is the target
+ *                     that moves.  The estimate is T = T_REF_TGT, starting at the identity.
+ *   outer iteration   k = 1 .. max_outer (max_correspondence_iterations; iterate_correspondences false is max_outer = 1).  For each
+ *                     target edge e, x = T e and its 2 nearest reference edge points a, b by (d^2, index): kept iff the cloud has 2
+ *                     points, the farther has d^2 < max_corr^2 and a != b as points.  For each target surface point the same with its
+ *                     3 nearest reference surface points a, b, c: kept iff all three lie below the threshold and n = (b - a) x (c - a),
+ *                     as computed, is not the zero vector.  The strict threshold and the treatment of exact degeneracy only are the
+ *                     library's choices.  A measurement stores the target point before T.  n_edge + n_surf < min_measurements:
+ *                     TOO_FEW_MEASUREMENTS, T as it was before this outer iteration (the reference's Match() returns false).
+ *   inner solve       Ceres' Levenberg-Marquardt, as bsgpu_localize_frames restates it for one pose (Jacobi scaling, clamped
+ *                     diagonal, the rho test, the radius update, the three tolerances over the ambient (q, p)), from the current T with
+ *                     the fields of *inner that bsgpu_localize_frames reads; trust_region_strategy_type must be LM.  The pose is
+ *                     (q, p) with x = R(q) e + p, tangent [p, theta], q <- q (x) exp(theta), the exponential from its series (no
+ *                     library sine).  One scalar residual per measurement: edge r = |(x - a) x (x - b)| / |a - b|, surface
+ *                     r = n . (x - a) / |n|; loss rho(r^2) with loss_kind TRIVIAL or HUBER(loss_a) (shipped: ceres_config.json HUBER,
+ *                     scaling 1, 50 iterations, tolerances 1e-8 / 1e-10 / 1e-8).  An edge residual that is exactly 0 has a zero Jacobian
+ *                     row (the library's choice: automatic differentiation of the square root at 0 has none).  An unusable inner solve:
+ *                     SOLVER_FAILED, T as before this outer iteration.
+ *   outer criterion   in this order: k >= max_outer: MAX_ITERATIONS (a success, as in the reference); otherwise with
+ *                     D = inv(T_before) T: |D.t| < conv_translation_m and the rotation angle of D < conv_rotation_deg (both): TRANSFORM.
+ *                     The angle test compares (tr D.R - 1) / 2 with the cosine of the threshold, which the host takes once; the device
+ *                     calls no acos, atan, sin, cos or log.  (A threshold of 0 is never met.)
+ * Outputs per pair: T_refest_ref (12) = inv(T), what matcher_->GetResult() is (multi_scan_registration.cpp:522); T_ref_tgt (optional, 12)
+ * = T T_init (:523-524); cov (optional, 36): the last inner solve's (J^T J)^-1 at its final pose, J loss-corrected, tangent order
+ * [p, theta], standing for matcher_->GetCovariance() (:528) — NaN unless the status is a success, and NaN for a singular J^T J; cost
+ * (optional): the last inner solve's final cost; n_edge, n_surf (optional): kept in the last outer iteration; n_iters (optional): outer
+ * iterations applied; n_inner (optional): LM iterations in total; status (BSGPU_LOAM_*; converged iff MAX_ITERATIONS or TRANSFORM).
+ * n_pairs == 0 does nothing; empty clouds give TOO_FEW_MEASUREMENTS with T = I.
+ * Both searches are exact (a dense grid of cell edge grid_cell over each reference cloud, searched in shells): grid_cell is a performance
+ * knob that no bit depends on.  Every sum over measurements has a fixed order (the target features, edges then surfaces, in chunks), so
+ * a pair's bits depend neither on its neighbours in the call nor on grid_cell.  A pair is one workgroup: a pair far above a local map's
+ * few thousand features runs on one compute unit, serially over rounds of features.
+ * INVALID: everything bsgpu_register_scans refuses (per table: ref_edge_start, ref_surf_start, tgt_edge_start, tgt_surf_start), and
+ * min_measurements < 1, max_outer < 1, a negative or NaN conv_translation_m or conv_rotation_deg, conv_rotation_deg >= 180, grid_cell not
+ * positive and finite, an unknown loss_kind, loss_a not positive and finite for HUBER, inner == NULL.  UNSUPPORTED: the grid caps of
+ * bsgpu_register_scans_gicp; max_outer > BSGPU_LOAM_MAX_OUTER; inner->max_num_iterations > BSGPU_LOAM_MAX_INNER; more than
+ * BSGPU_LOAM_MAX_FEATURES target features in one pair (a pair is one workgroup: the cap bounds a launch's length); BSGPU_LOSS_CAUCHY (its
+ * logarithm is not the same function on host and device); a trust-region strategy other than LM.
+ * Nothing is written unless the call succeeds; bsgpu_register_scans_error says what this thread's last failed call objected to,
+ * prefixed "register_scans_loam: ".  */
+enum { BSGPU_LOAM_MAX_ITERATIONS = 1, BSGPU_LOAM_TRANSFORM = 2, BSGPU_LOAM_TOO_FEW_MEASUREMENTS = 5, BSGPU_LOAM_SOLVER_FAILED = 6 };
+#define BSGPU_LOAM_MAX_OUTER 100
+#define BSGPU_LOAM_MAX_INNER 1000
+#define BSGPU_LOAM_MAX_FEATURES 65536
+int bsgpu_register_scans_loam(int device, int32_t n_pairs, const int32_t* ref_edge_start, const double* ref_edges, const int32_t* ref_surf_start,
+                              const double* ref_surfs, const int32_t* tgt_edge_start, const double* tgt_edges, const int32_t* tgt_surf_start,
+                              const double* tgt_surfs, const double* T_init, double max_corr, int32_t min_measurements, int32_t max_outer,
+                              double conv_translation_m, double conv_rotation_deg, const bsgpu_options* inner, int32_t loss_kind, double loss_a,
+                              double grid_cell, double* T_refest_ref, double* T_ref_tgt, double* cov, double* cost, int32_t* n_edge,
+                              int32_t* n_surf, int32_t* n_iters, int32_t* n_inner, int32_t* status);
+
 /* Scan Context place recognition — the descriptors and the search of RelocCandidateSearchScanContext::FindRelocCandidates
  * (bs_models/src/lib/reloc/reloc_candidate_search_scan_context.cpp:117-150): the step that decides which scan pairs
  * AlignSubmapsFromScanMatches (:210-262) hands to the matcher (bsgpu_register_scans).  Two stateless calls, so that a caller can keep
