@@ -115,7 +115,7 @@ SYMBOLS = [
     "reprojection_errors", "preintegrate", "triangulate", "time_reproj_jacobian_ms", "reproj_jacobian_bytes", "dense_solve", "plan_info",
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
     "covariance_requests", "localize_frames", "num_factorizations", "essential_ransac", "absolute_pose_ransac",
-    "relative_pose_ransac", "inertial_alignment", "register_scans", "register_scans_error", "register_scans_gicp", "register_scans_loam", "backsub_tangent_table",
+    "relative_pose_ransac", "inertial_alignment", "register_scans", "register_scans_error", "register_scans_gicp", "register_scans_loam", "extract_loam_features", "backsub_tangent_table",
     "scan_context_describe", "scan_context_match", "scan_context_error",
 ]
 
@@ -168,6 +168,15 @@ LOAM_DEFAULTS = dict(max_corr=0.5, min_measurements=30, max_outer=10, conv_trans
                      inner=dict(max_num_iterations=50, function_tolerance=1e-8, gradient_tolerance=1e-10, parameter_tolerance=1e-8))
 REGISTER_SCANS_LOAM_ARGTYPES = [C.c_int, C.c_int32, _ip, _dp, _ip, _dp, _ip, _dp, _ip, _dp, _dp, C.c_double, C.c_int32, C.c_int32, C.c_double,
                                 C.c_double, C.POINTER(Options), C.c_int32, C.c_double, C.c_double, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip]
+#: bsgpu_extract_loam_features: the labels, the axes, the limits, the reference's shipped parameters (config/matchers/loam_vlp16.json;
+#: loam_vlp16_init.json: 3 regions, curvature_region 3, 15 less sharp) and the typed prototype
+LOAM_DROPPED, LOAM_LESS_FLAT, LOAM_FLAT, LOAM_LESS_SHARP, LOAM_SHARP = -1, 0, 1, 2, 3
+AXIS_X, AXIS_Y, AXIS_Z = 0, 1, 2
+LOAM_MAX_RINGS, LOAM_MAX_RING_POINTS, LOAM_MAX_CURVATURE_REGION, LOAM_MAX_REGIONS = 128, 4096, 16, 64
+LOAM_FEATURE_DEFAULTS = dict(number_of_beams=16, fov_deg=30.0, vertical_axis=AXIS_Z, n_feature_regions=6, curvature_region=5, max_corner_sharp=2,
+                             max_corner_less_sharp=20, max_surface_flat=4, surface_curvature_threshold=0.1, downsample_less_flat_features=0)
+EXTRACT_LOAM_FEATURES_ARGTYPES = [C.c_int, C.c_int32, _ip, _dp, _ip, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_int32, C.c_double, C.c_int32, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _dp]
 #: bsgpu_scan_context_describe / bsgpu_scan_context_match: the descriptor's shape, the limits, the reference's shipped parameters
 #: (SCManager's LIDAR_HEIGHT, PC_MAX_RADIUS, NUM_CANDIDATES_FROM_TREE, SEARCH_RATIO, SC_DIST_THRES, recalled) and the typed prototypes
 SC_RINGS, SC_SECTORS, SC_MAX_CANDIDATES, SC_MAX_TREE_CANDIDATES, SC_MAX_SCAN_POINTS = 20, 60, 65536, 64, 65535 * 4096

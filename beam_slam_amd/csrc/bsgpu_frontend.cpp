@@ -1,5 +1,5 @@
 // The front-end entry points of the C-ABI (include/bsgpu.h): bsgpu_preintegrate, bsgpu_inertial_alignment, bsgpu_register_scans,
-// bsgpu_register_scans_gicp, bsgpu_register_scans_loam, bsgpu_scan_context_describe, bsgpu_scan_context_match, bsgpu_triangulate, bsgpu_localize_frames and the three RANSACs.  Each checks its arguments, describes its arrays as a StageLayout (staging.h:
+// bsgpu_register_scans_gicp, bsgpu_register_scans_loam, bsgpu_extract_loam_features, bsgpu_scan_context_describe, bsgpu_scan_context_match, bsgpu_triangulate, bsgpu_localize_frames and the three RANSACs.  Each checks its arguments, describes its arrays as a StageLayout (staging.h:
 // [inputs | outputs | scratch] in one device allocation), runs one kernel between one copy in and one copy out, and hands the
 // results to the caller's arrays: nothing is written to them unless the call succeeds.
 #include <algorithm>
@@ -12,6 +12,7 @@
 #include "point_grid.h"
 #include "inertial_align.h"
 #include "loam.h"
+#include "loam_features.h"
 #include "scan_context.h"
 #include "staging.h"
 
@@ -399,6 +400,118 @@ int bsgpu_register_scans_loam(int device, int32_t n_pairs, const int32_t* ref_ed
   return BSGPU_OK;
 } catch (...) {
   try { g_register_scans_error = "register_scans_loam: out of host memory"; } catch (...) {}
+  return api_exception(nullptr);
+}
+
+int bsgpu_extract_loam_features(int device, int32_t n_scans, const int32_t* scan_start, const double* points, const int32_t* ring,
+                                int32_t number_of_beams, double fov_deg, int32_t vertical_axis, int32_t n_feature_regions,
+                                int32_t curvature_region, int32_t max_corner_sharp, int32_t max_corner_less_sharp, int32_t max_surface_flat,
+                                double surface_curvature_threshold, int32_t downsample_less_flat_features, int32_t* edge_start,
+                                int32_t* edge_index, double* edge_points, int32_t* surf_start, int32_t* surf_index, double* surf_points,
+                                int32_t* weak_edge_start, int32_t* weak_edge_index, double* weak_edge_points, int32_t* weak_surf_start,
+                                int32_t* weak_surf_index, double* weak_surf_points, int32_t* label, double* curvature) try {
+  const char* const me = "extract_loam_features";
+  const auto refuse = [me](int code, const char* why) { return refuse_scans(code, me, why); };
+  const bool weak = weak_edge_start || weak_edge_index || weak_edge_points || weak_surf_start || weak_surf_index || weak_surf_points;
+  if (n_scans < 0 || !scan_start || !edge_start || !edge_index || !surf_start || !surf_index) return refuse(BSGPU_ERR_INVALID, "null argument");
+  if (weak && (!weak_edge_start || !weak_edge_index || !weak_surf_start || !weak_surf_index))
+    return refuse(BSGPU_ERR_INVALID, "the weak clouds come as a group: both start tables and both index arrays, or none");
+  if (number_of_beams < 1) return refuse(BSGPU_ERR_INVALID, "number_of_beams must be at least 1");
+  if (n_feature_regions < 1) return refuse(BSGPU_ERR_INVALID, "n_feature_regions must be at least 1");
+  if (curvature_region < 1) return refuse(BSGPU_ERR_INVALID, "curvature_region must be at least 1");
+  if (max_corner_sharp < 0 || max_corner_less_sharp < 0 || max_surface_flat < 0)
+    return refuse(BSGPU_ERR_INVALID, "max_corner_sharp, max_corner_less_sharp and max_surface_flat must not be negative");
+  if (!(fov_deg > 0.0) || !(fov_deg < 180.0)) return refuse(BSGPU_ERR_INVALID, "fov_deg must lie in (0, 180)");
+  if (!std::isfinite(surface_curvature_threshold)) return refuse(BSGPU_ERR_INVALID, "surface_curvature_threshold must be finite");
+  if (vertical_axis < BSGPU_AXIS_X || vertical_axis > BSGPU_AXIS_Z) return refuse(BSGPU_ERR_INVALID, "unknown vertical_axis");
+  if (number_of_beams > BSGPU_LOAM_MAX_RINGS) return refuse(BSGPU_ERR_UNSUPPORTED, "number_of_beams exceeds BSGPU_LOAM_MAX_RINGS");
+  if (curvature_region > BSGPU_LOAM_MAX_CURVATURE_REGION) return refuse(BSGPU_ERR_UNSUPPORTED, "curvature_region exceeds BSGPU_LOAM_MAX_CURVATURE_REGION");
+  if (n_feature_regions > BSGPU_LOAM_MAX_REGIONS) return refuse(BSGPU_ERR_UNSUPPORTED, "n_feature_regions exceeds BSGPU_LOAM_MAX_REGIONS");
+  if (downsample_less_flat_features != 0)
+    return refuse(BSGPU_ERR_UNSUPPORTED, "downsample_less_flat_features is not supported (a voxel grid over features that every shipped matcher ignores)");
+  static_assert(BSGPU_LOAM_MAX_RINGS == kLoamMaxRings && BSGPU_LOAM_MAX_RING_POINTS == kLoamMaxRingPoints &&
+                BSGPU_LOAM_MAX_CURVATURE_REGION == kLoamMaxCurvatureRegion && BSGPU_LOAM_MAX_REGIONS == kLoamMaxRegions, "the header's caps are loam_features.h's");
+  static_assert(BSGPU_LOAM_DROPPED == LOAM_FEAT_DROPPED && BSGPU_LOAM_LESS_FLAT == LOAM_FEAT_LESS_FLAT && BSGPU_LOAM_FLAT == LOAM_FEAT_FLAT &&
+                BSGPU_LOAM_LESS_SHARP == LOAM_FEAT_LESS_SHARP && BSGPU_LOAM_SHARP == LOAM_FEAT_SHARP, "the header's labels are loam_features.h's");
+  switch (check_start_table(scan_start, n_scans, INT_MAX, [&](int k) { return scan_start[k + 1] == scan_start[k] || points; })) {
+    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "scan_start[0] must be 0");
+    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "scan_start must be non-decreasing");
+    case kStartBadItem: return refuse(BSGPU_ERR_INVALID, "null points");
+    default: break;
+  }
+  if (n_scans == 0) return BSGPU_OK;
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "hipSetDevice failed"); }
+  const size_t ns = (size_t)n_scans, np = (size_t)scan_start[n_scans], beams = (size_t)number_of_beams, regions = (size_t)n_feature_regions;
+  LoamFeatParams P;
+  P.beams = number_of_beams; P.regions = n_feature_regions; P.c = curvature_region;
+  P.max_sharp = max_corner_sharp; P.max_less_sharp = max_corner_less_sharp; P.max_flat = max_surface_flat;
+  P.axis = vertical_axis; P.threshold = surface_curvature_threshold;
+  std::vector<double> bound(beams + 1);
+  loam_feat_bounds(number_of_beams, fov_deg, bound.data());
+  // a ring's picks are distinct positions, so they are at most its points
+  const size_t per_region = (size_t)std::min(max_corner_less_sharp, kLoamMaxRingPoints) + (size_t)std::min(max_surface_flat, kLoamMaxRingPoints);
+  const size_t pick_cap = std::min((size_t)kLoamMaxRingPoints, regions * per_region);
+  StageLayout L;
+  const int s_ss = L.in(scan_start, 4 * (ns + 1)), s_pts = L.in(points, 24 * np), s_ring = L.in(ring, ring ? 4 * np : 0), s_bd = L.in(bound.data(), 8 * (beams + 1));
+  // per point: ring, label, curvature; per (scan, ring): the picks and two counts per region; the overflow flag.  The host packs below.
+  const int s_rid = L.out(nullptr, 4 * np), s_lab = L.out(label, 4 * np), s_cv = L.out(curvature, 8 * np), s_pk = L.out(nullptr, 4 * ns * beams * pick_cap),
+            s_cnt = L.out(nullptr, 8 * ns * beams * regions), s_of = L.out(nullptr, 4);
+  DeviceStage D(L);
+  if (!D) return refuse(BSGPU_ERR_DEVICE, "out of device memory");
+  const auto I = [&](int s) { return D.ptr<int>(s); };
+  const hipError_t e = D.run(nullptr, [&] {
+    launch_extract_loam_features(nullptr, n_scans, (int)np, I(s_ss), D.ptr<double>(s_pts), ring ? I(s_ring) : nullptr, P, D.ptr<double>(s_bd),
+                                 (int)pick_cap, I(s_rid), I(s_lab), D.ptr<double>(s_cv), I(s_pk), I(s_cnt), I(s_of));
+  });
+  if (e != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "device error"); }
+  if (*L.out_image<int32_t>(s_of) != 0) return refuse(BSGPU_ERR_UNSUPPORTED, "a ring has more than BSGPU_LOAM_MAX_RING_POINTS points");
+  const int32_t *rid = L.out_image<int32_t>(s_rid), *lab = L.out_image<int32_t>(s_lab), *pk = L.out_image<int32_t>(s_pk), *cnt = L.out_image<int32_t>(s_cnt);
+  L.scatter();      // label and curvature
+  // The packing: within a scan ring, then region, then pick order; LESS_FLAT by ring and position.
+  struct Cloud { int32_t *start, *index; double* pts; int32_t n; };
+  Cloud sharp{edge_start, edge_index, edge_points, 0}, flat{surf_start, surf_index, surf_points, 0},
+        less_sharp{weak_edge_start, weak_edge_index, weak_edge_points, 0}, less_flat{weak_surf_start, weak_surf_index, weak_surf_points, 0};
+  const auto put = [&](Cloud& C, size_t scan, int32_t i) {
+    C.index[C.n] = i;
+    if (C.pts) std::memcpy(C.pts + 3 * (size_t)C.n, points + 3 * ((size_t)scan_start[scan] + (size_t)i), 24);
+    ++C.n;
+  };
+  std::vector<int32_t> at(beams + 1);
+  sharp.start[0] = 0; flat.start[0] = 0;
+  if (weak) { less_sharp.start[0] = 0; less_flat.start[0] = 0; }
+  for (size_t s = 0; s < ns; ++s) {
+    for (size_t r = 0; r < beams; ++r) {
+      const int32_t* p = pk + (s * beams + r) * pick_cap;
+      for (size_t j = 0; j < regions; ++j) {
+        const int32_t ne = cnt[2 * ((s * beams + r) * regions + j)], nf = cnt[2 * ((s * beams + r) * regions + j) + 1];
+        for (int32_t k = 0; k < ne; ++k, ++p) {
+          if (k < max_corner_sharp) put(sharp, s, *p);
+          else if (weak) put(less_sharp, s, *p);
+        }
+        for (int32_t k = 0; k < nf; ++k, ++p) put(flat, s, *p);
+      }
+    }
+    sharp.start[s + 1] = sharp.n; flat.start[s + 1] = flat.n;
+    if (!weak) continue;
+    less_sharp.start[s + 1] = less_sharp.n;
+    // a stable partition of the scan's LESS_FLAT points by ring
+    const size_t s0 = (size_t)scan_start[s], s1 = (size_t)scan_start[s + 1];
+    std::fill(at.begin(), at.end(), 0);
+    for (size_t i = s0; i < s1; ++i) if (lab[i] == LOAM_FEAT_LESS_FLAT) ++at[(size_t)rid[i] + 1];
+    for (size_t r = 0; r < beams; ++r) at[r + 1] += at[r];
+    const int32_t base = less_flat.n;
+    for (size_t i = s0; i < s1; ++i) {
+      if (lab[i] != LOAM_FEAT_LESS_FLAT) continue;
+      const int32_t k = base + at[(size_t)rid[i]]++;
+      less_flat.index[k] = (int32_t)(i - s0);
+      if (less_flat.pts) std::memcpy(less_flat.pts + 3 * (size_t)k, points + 3 * i, 24);
+    }
+    less_flat.n = base + at[beams - 1];
+    less_flat.start[s + 1] = less_flat.n;
+  }
+  return BSGPU_OK;
+} catch (...) {
+  try { g_register_scans_error = "extract_loam_features: out of host memory"; } catch (...) {}
   return api_exception(nullptr);
 }
 

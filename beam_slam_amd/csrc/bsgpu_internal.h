@@ -591,6 +591,14 @@ void launch_register_scans_loam(hipStream_t s, int n_pairs, int max_points, int 
                                 const double* T_cloud, const PointGrid* grids, const int* feat_start, const double* tgt, const double* T_init,
                                 const LoamParams& P, double* out, int* out_i, double* rq, int* tcell, int* cells, int* tile_sum, double* rec,
                                 double* tq, int* corr);
+// LOAM feature extraction (k_loam_features.hip, bsgpu_extract_loam_features): a lane per point for validity and ring, then one workgroup
+// per (scan, ring).  bound: beams + 1 tangents (loam_feat_bounds; read only when ring is null).  Per point of the call: ring_id, label,
+// curvature.  Per (scan, ring): pick_cap slots of picks (indices into the scan, in pick order) and 2 counts per region (edges taken,
+// surfaces taken).  overflow (one int, cleared first): set when a ring has more than kLoamMaxRingPoints points.
+struct LoamFeatParams;
+void launch_extract_loam_features(hipStream_t s, int n_scans, int n_points, const int* scan_start, const double* points, const int* ring,
+                                  const LoamFeatParams& P, const double* bound, int pick_cap, int* ring_id, int* label, double* curvature,
+                                  int* picks, int* counts, int* overflow);
 // Scan Context place recognition (k_scan_context.hip, bsgpu_scan_context_describe / _match).  Inputs as the C-ABI's, on the device, plus
 // what the host derives: member_agg (a member's aggregate), max_chunks (chunks of kScChunk points of the longest scan a member names),
 // query_set (a query's set), pair_start (n_queries: where a query's (query, candidate) entries begin), R (the refinement radius).

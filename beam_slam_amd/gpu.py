@@ -224,6 +224,65 @@ def register_scans_loam(ref_edge_start, ref_edges, ref_surf_start, ref_surfs, tg
     return out
 
 
+def extract_loam_features(scan_start, points, ring=None, weak=True, labels=True, curvature=True, with_points=True, device=0, **params):
+    """bsgpu_extract_loam_features: LOAM feature extraction (the reference's LoamFeatureExtractor in its shipped configuration) for a
+    batch of scans.  Scan s is points[scan_start[s]:scan_start[s+1]]; ring: optional, one per point.  params: the keys of
+    capi.LOAM_FEATURE_DEFAULTS (vertical_axis also as "X", "Y" or "Z").  Returns a dict of arrays: edge_start, edge_index, edge_points
+    (SHARP) and surf_* (FLAT) — the edges / surfs arrays of register_scans_loam —, with weak the same for weak_edge_* (LESS_SHARP) and
+    weak_surf_* (LESS_FLAT), with labels label and with curvature curvature, per input point.  with_points false leaves the *_points out."""
+    import numpy as np
+    unknown = set(params) - set(capi.LOAM_FEATURE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"extract_loam_features: unknown parameters {sorted(unknown)}")
+    P = dict(capi.LOAM_FEATURE_DEFAULTS, **params)
+    if isinstance(P["vertical_axis"], str):
+        P["vertical_axis"] = {"X": capi.AXIS_X, "Y": capi.AXIS_Y, "Z": capi.AXIS_Z}.get(P["vertical_axis"].upper(), -1)
+    ss = np.ascontiguousarray(scan_start, np.int32).reshape(-1)
+    pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    rg = None if ring is None else np.ascontiguousarray(ring, np.int32).reshape(-1)
+    S = ss.size - 1
+    if S < 0 or (rg is not None and rg.size != pts.shape[0]):
+        raise capi.SolverError(capi.ERR_INVALID, "extract_loam_features: array sizes do not agree")
+    if int(ss.max()) > pts.shape[0]:
+        raise capi.SolverError(capi.ERR_INVALID, "extract_loam_features: scan_start names more points than were passed")
+    # the capacities of the contract, for the whole call
+    n = pts.shape[0]
+    cells = S * max(int(P["number_of_beams"]), 0) * max(int(P["n_feature_regions"]), 0)
+    sharp, less = max(int(P["max_corner_sharp"]), 0), max(int(P["max_corner_less_sharp"]), 0)
+    cap = dict(edge=min(n, cells * min(sharp, less)), surf=min(n, cells * max(int(P["max_surface_flat"]), 0)), weak_edge=min(n, cells * max(less - sharp, 0)),
+               weak_surf=n)
+    out = {}
+    for k in ("edge", "surf") + (("weak_edge", "weak_surf") if weak else ()):
+        out[k + "_start"] = np.zeros(S + 1, np.int32)
+        out[k + "_index"] = np.zeros(cap[k], np.int32)
+        if with_points:
+            out[k + "_points"] = np.zeros((cap[k], 3))
+    if labels:
+        out["label"] = np.zeros(n, np.int32)
+    if curvature:
+        out["curvature"] = np.zeros(n)
+    fn = lib().bsgpu_extract_loam_features
+    fn.argtypes = capi.EXTRACT_LOAM_FEATURES_ARGTYPES
+    _dp, _ip = capi._dp, capi._ip
+    d = lambda x: None if x is None else x.ctypes.data_as(_dp)
+    i = lambda x: None if x is None else x.ctypes.data_as(_ip)
+    clouds = []
+    for k in ("edge", "surf", "weak_edge", "weak_surf"):
+        clouds += [i(out.get(k + "_start")), i(out.get(k + "_index")), d(out.get(k + "_points"))]
+    rc = fn(device, S, i(ss), d(pts), i(rg), int(P["number_of_beams"]), float(P["fov_deg"]), int(P["vertical_axis"]), int(P["n_feature_regions"]),
+            int(P["curvature_region"]), int(P["max_corner_sharp"]), int(P["max_corner_less_sharp"]), int(P["max_surface_flat"]),
+            float(P["surface_curvature_threshold"]), int(P["downsample_less_flat_features"]), *clouds, i(out.get("label")), d(out.get("curvature")))
+    if rc != 0:
+        raise capi.SolverError(rc, register_scans_error())
+    for k in ("edge", "surf", "weak_edge", "weak_surf"):
+        if k + "_start" in out:
+            m = int(out[k + "_start"][-1]) if S > 0 else 0
+            out[k + "_index"] = out[k + "_index"][:m]
+            if with_points:
+                out[k + "_points"] = out[k + "_points"][:m]
+    return out
+
+
 def register_scans_error():
     """What this thread's last failed bsgpu_register_scans objected to."""
     fn = lib().bsgpu_register_scans_error

@@ -634,7 +634,7 @@ int bsgpu_register_scans_gicp(int device, int32_t n_pairs, const int32_t* ref_st
  * 158-188), RelocRefinementLoamRegistration (reloc_refinement_loam_registration.cpp:91-118), submap_alignment.cpp:76-96 and
  * global_map_batch_optimization.cpp:238-247 in the shipped configuration (config/matchers/loam_*.json, optimization/ceres_config.json).
  * The matcher's boundary is kept: LoamPointCloud in, transform and covariance out; feature extraction (LoamFeatureExtractor) is a
- * separate step and stays with the caller.  [EXT] libbeam's LoamMatcher, LoamScanRegistration, CeresPointToLineCostFunction and
+ * separate step: bsgpu_extract_loam_features, below.  [EXT] libbeam's LoamMatcher, LoamScanRegistration, CeresPointToLineCostFunction and
  * CeresPointToPlaneCostFunction are not in the reference checkout: everything below is RECALLED, not verified, and where the text says
  * "the library's choice" this library decides something the recollection leaves open.
  *   clouds            pair p has four packed-xyz clouds, start tables as in bsgpu_register_scans: the reference's edge and surface
@@ -693,6 +693,76 @@ int bsgpu_register_scans_loam(int device, int32_t n_pairs, const int32_t* ref_ed
                               double conv_translation_m, double conv_rotation_deg, const bsgpu_options* inner, int32_t loss_kind, double loss_a,
                               double grid_cell, double* T_refest_ref, double* T_ref_tgt, double* cov, double* cost, int32_t* n_edge,
                               int32_t* n_surf, int32_t* n_iters, int32_t* n_inner, int32_t* status);
+
+/* LOAM feature extraction for a batch of scans — the feature_extractor->ExtractFeatures(cloud) that every lidar scan goes through
+ * before a matcher sees it (bs_models/src/lib/lidar/scan_pose.cpp:34-37, 63-66, 92-95), in the shipped configuration
+ * (config/matchers/loam_*.json).  A raw revolution in, the four clouds of a LoamPointCloud out, the strong ones in exactly the layout
+ * bsgpu_register_scans_loam takes.  [EXT] libbeam's LoamFeatureExtractor is not in the reference checkout, only its call sites and its
+ * parameter files are: everything below is RECALLED from it and from the LOAM scan registration it derives from, not verified, and
+ * where the text says "the library's choice" this library decides something the recollection leaves open.  Arithmetic is FP64 (the
+ * original bins float points); every squared length is (x^2 + y^2) + z^2, no product is fused.
+ *   scans             scan s is points[3 scan_start[s] .. 3 scan_start[s+1]), packed xyz, start table as in bsgpu_register_scans; ring
+ *                     (optional) one int32 per point.
+ *   validity          a point is dropped if a coordinate is not finite or |p|^2 < 1e-4.
+ *   ring              with ring given: that value, dropped outside [0, number_of_beams).  With ring == NULL, from the elevation: v the
+ *                     coordinate along vertical_axis (BSGPU_AXIS_*), h the root of the other two squared, the angle in degrees,
+ *                     t = (angle + fov_deg / 2) (beams - 1) / fov_deg + 0.5, the ring trunc(t), dropped outside [0, beams).  The device
+ *                     decides this by comparisons only: the host takes the tangents of the beams + 1 boundary angles (t = -1, 1, 2 ..
+ *                     beams) once per call and a point is compared as v against tan(beta) h (a boundary at or beyond +-90 degrees is
+ *                     infinite).  This form is the library's choice; no atan runs on the device.  A point within rounding of a
+ *                     boundary may therefore fall to the other side than an atan would put it.
+ *   ring order        a ring's points keep their order of arrival in the scan (a stable partition).  A ring of n points with
+ *                     n - 1 <= 2 c, c = curvature_region, is skipped whole.
+ *   unreliable        for i in [c, n - 1 - c), dn = |p_{i+1} - p_i|^2, dp = |p_i - p_{i-1}|^2: if dn > 0.1, with r1 = |p_i|,
+ *                     r2 = |p_{i+1}|: r1 > r2 and |p_{i+1} - p_i (r2 / r1)| / r2 < 0.1 marks i - c .. i as picked; r1 <= r2 and
+ *                     |p_{i+1} (r1 / r2) - p_i| / r1 < 0.1 marks i + 1 .. i + c + 1.  If dn > 0.0002 |p_i|^2 and dp > 0.0002 |p_i|^2, i
+ *                     is marked.
+ *   curvature         for i in [c, n - c): s = -2 c p_i, then for j = 1 .. c in that order s += p_{i+j}, s += p_{i-j}; the curvature is
+ *                     |s|^2.
+ *   regions           L = n - 1 - 2 c, G = n_feature_regions; region j covers sp = c + (L j) / G .. ep = c + (L (j + 1)) / G - 1 in
+ *                     integer division; a region with ep <= sp is skipped.  The regions of a ring are processed in order, because a
+ *                     pick marks neighbours across a region's border.
+ *   picks             the total order is the key (curvature, position in the ring); that ties go by position is the library's choice
+ *                     (the original's sort leaves them open).  Edges: from the largest key down, until max_corner_less_sharp are taken
+ *                     or the region is exhausted; a point is taken iff it is not picked and its curvature >
+ *                     surface_curvature_threshold; the first max_corner_sharp taken are SHARP, the rest LESS_SHARP.  Surfaces: from the
+ *                     smallest key up, until max_surface_flat are taken; taken iff not picked and curvature < the threshold: FLAT.  A
+ *                     taken point is marked as picked: itself, then i + k for k = 1 .. c, stopping at the ring's end or when
+ *                     |p_{i+k} - p_{i+k-1}|^2 > 0.05, and the same backwards.  Every other point of a processed region is LESS_FLAT.
+ * Outputs, packed with start tables of n_scans + 1 entries, within a scan by ring, then region, then pick order: the STRONG edges
+ * (SHARP: edge_start, edge_index — the point's index within its scan —, edge_points, optional: packed xyz, the input's bits) and the
+ * STRONG surfaces (FLAT: surf_*), which are the edges / surfs arrays of bsgpu_register_scans_loam.  Optional as a group (all six NULL,
+ * or both start tables and both index arrays given): the WEAK clouds LESS_SHARP (weak_edge_*) and LESS_FLAT (weak_surf_*, by ring and
+ * position).  They are disjoint from the strong ones — a caller who wants the original's supersets concatenates; the library's choice.
+ * label (optional, per input point): BSGPU_LOAM_DROPPED for a point that is invalid, without a ring, in a skipped ring or outside every
+ * processed region, else its class.  curvature (optional, per input point): NaN where none is defined.
+ * Capacities per scan, which the caller provides: strong edges beams G min(max_corner_sharp, max_corner_less_sharp), weak edges
+ * beams G max(max_corner_less_sharp - max_corner_sharp, 0), strong surfaces beams G max_surface_flat, weak surfaces the scan's points
+ * (none of them more than the scan's points).
+ * n_scans == 0 does nothing; an empty scan gives empty clouds; a scan's outputs depend on nothing else in the call, and no output
+ * depends on how the device schedules its lanes.  One workgroup per (scan, ring): a lone revolution uses as many compute units as it
+ * has rings.
+ * OUT OF SCOPE: the voxel filter of the weak surfaces (downsample_less_flat_features must be 0), deskewing, intensity and time fields,
+ * and keeping the features on the device for the matcher: the two calls are chained through host arrays.
+ * INVALID: NULL where an array is needed, a weak group given in part, everything bsgpu_register_scans refuses of a start table,
+ * number_of_beams, n_feature_regions or curvature_region < 1, a negative count, fov_deg not in (0, 180), a threshold that is not
+ * finite, an unknown vertical_axis.  UNSUPPORTED: number_of_beams > BSGPU_LOAM_MAX_RINGS, a ring of more than
+ * BSGPU_LOAM_MAX_RING_POINTS points, curvature_region > BSGPU_LOAM_MAX_CURVATURE_REGION, n_feature_regions > BSGPU_LOAM_MAX_REGIONS,
+ * downsample_less_flat_features != 0.  Nothing is written unless the call succeeds; bsgpu_register_scans_error says what this
+ * thread's last failed call objected to, prefixed "extract_loam_features: ".  */
+enum { BSGPU_LOAM_DROPPED = -1, BSGPU_LOAM_LESS_FLAT = 0, BSGPU_LOAM_FLAT = 1, BSGPU_LOAM_LESS_SHARP = 2, BSGPU_LOAM_SHARP = 3 };
+enum { BSGPU_AXIS_X = 0, BSGPU_AXIS_Y = 1, BSGPU_AXIS_Z = 2 };
+#define BSGPU_LOAM_MAX_RINGS 128
+#define BSGPU_LOAM_MAX_RING_POINTS 4096
+#define BSGPU_LOAM_MAX_CURVATURE_REGION 16
+#define BSGPU_LOAM_MAX_REGIONS 64
+int bsgpu_extract_loam_features(int device, int32_t n_scans, const int32_t* scan_start, const double* points, const int32_t* ring,
+                                int32_t number_of_beams, double fov_deg, int32_t vertical_axis, int32_t n_feature_regions,
+                                int32_t curvature_region, int32_t max_corner_sharp, int32_t max_corner_less_sharp, int32_t max_surface_flat,
+                                double surface_curvature_threshold, int32_t downsample_less_flat_features, int32_t* edge_start,
+                                int32_t* edge_index, double* edge_points, int32_t* surf_start, int32_t* surf_index, double* surf_points,
+                                int32_t* weak_edge_start, int32_t* weak_edge_index, double* weak_edge_points, int32_t* weak_surf_start,
+                                int32_t* weak_surf_index, double* weak_surf_points, int32_t* label, double* curvature);
 
 /* Scan Context place recognition — the descriptors and the search of RelocCandidateSearchScanContext::FindRelocCandidates
  * (bs_models/src/lib/reloc/reloc_candidate_search_scan_context.cpp:117-150): the step that decides which scan pairs

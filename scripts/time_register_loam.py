@@ -2,8 +2,8 @@
 config/optimization/ceres_config.json, capi.LOAM_DEFAULTS): bsgpu_register_scans_loam scan-to-scan (a scan's features against the
 previous scan's) and scan-to-map (against the features of 20 earlier scans in one frame), each as 1 pair and as 10 pairs in one call.
 The scans are VLP-16 revolutions (16 rings x 1 812 azimuths) cast from inside the 20 x 14 x 5 m room of the tests, 1 cm range noise; the
-features come from a simple curvature picker (per ring and each of 6 regions the 2 sharpest points as edges and the 4 flattest as
-surfaces: 192 + 384 per scan, the counts of the shipped extractor's strong features) — scaffolding, not the reference's extractor.
+features are the library's own: bsgpu_extract_loam_features at the shipped parameters (capi.LOAM_FEATURE_DEFAULTS), ring by elevation,
+all scans of the path in one call, and of its output the STRONG clouds, which is what every shipped matcher file registers.
 Each figure is taken twice: HIP events recorded around the blocking call (the device clock over upload, kernels and download), and the
 host clock around the same call.  Median and range of --reps calls after a warm-up.  Beside them the wall time of the shared header's
 serial loop (loam.h on one core, g++ -O2 -march=native) on the same inputs: the only baseline there is, since libbeam's matcher is not
@@ -29,24 +29,11 @@ from time_register_scans import HipEvents, revolution, stats  # noqa: E402
 from time_register_gicp import compose, inverse, pose  # noqa: E402
 from beam_slam_amd import capi, gpu  # noqa: E402
 
-RINGS, AZIMUTHS, REGIONS, HALF = 16, 1812, 6, 5
-
-
-def features(cloud, n_sharp=2, n_flat=4):
-    """(edges, surfaces) of one revolution: curvature |sum_{j = -5 .. 5} (p_{i+j} - p_i)|^2 / |p_i|^2 along each ring; per ring and region
-    the n_sharp largest and the n_flat smallest"""
-    P = cloud.reshape(RINGS, AZIMUTHS, 3)
-    acc = np.zeros_like(P)
-    for j in range(-HALF, HALF + 1):
-        acc += np.roll(P, j, axis=1) - P
-    curv = (acc ** 2).sum(axis=2) / (P ** 2).sum(axis=2)
-    edges, surfs = [], []
-    for ring in range(RINGS):
-        for reg in np.array_split(np.arange(AZIMUTHS), REGIONS):
-            order = reg[np.argsort(curv[ring, reg], kind="stable")]
-            edges.append(P[ring, order[-n_sharp:]])
-            surfs.append(P[ring, order[:n_flat]])
-    return np.concatenate(edges), np.concatenate(surfs)
+def features(clouds):
+    """[(edges, surfaces)] of the revolutions: the strong clouds of one bsgpu_extract_loam_features call"""
+    out = gpu.extract_loam_features(np.cumsum([0] + [len(c) for c in clouds]), np.concatenate(clouds), weak=False, labels=False, curvature=False)
+    es, ss = out["edge_start"], out["surf_start"]
+    return [(out["edge_points"][es[k]:es[k + 1]].copy(), out["surf_points"][ss[k]:ss[k + 1]].copy()) for k in range(len(clouds))]
 
 
 def cpu_serial(groups, a, params):
@@ -76,7 +63,7 @@ def main():
     # within reach and the matcher has a correction to find
     n_scans = a.map_scans + a.pairs
     poses = [pose([0.0, 0.0, 0.01 * k], [-2.0 + 0.12 * k, 0.02 * k, 0.0]) for k in range(n_scans + 1)]
-    feats = [features(revolution(T, rng)) for T in poses]
+    feats = features([revolution(T, rng) for T in poses])
     drift = pose([0.003, -0.002, 0.006], [0.04, -0.03, 0.01])
     scan_pairs, map_pairs = [], []
     for k in range(a.map_scans, a.map_scans + a.pairs):
