@@ -115,7 +115,7 @@ SYMBOLS = [
     "reprojection_errors", "preintegrate", "triangulate", "time_reproj_jacobian_ms", "reproj_jacobian_bytes", "dense_solve", "plan_info",
     "profile_step", "time_eval_ms", "eval_bytes", "bsr_info", "covariance_joint", "update_marginal", "solve_batch", "batch_stats", "set_plan_preference",
     "covariance_requests", "localize_frames", "num_factorizations", "essential_ransac", "absolute_pose_ransac",
-    "relative_pose_ransac", "inertial_alignment", "register_scans", "register_scans_error", "register_scans_gicp", "register_scans_loam", "extract_loam_features", "backsub_tangent_table",
+    "relative_pose_ransac", "inertial_alignment", "register_scans", "register_scans_error", "register_scans_gicp", "register_scans_loam", "extract_loam_features", "build_registration_maps", "backsub_tangent_table",
     "scan_context_describe", "scan_context_match", "scan_context_error",
 ]
 
@@ -177,6 +177,10 @@ LOAM_FEATURE_DEFAULTS = dict(number_of_beams=16, fov_deg=30.0, vertical_axis=AXI
                              max_corner_less_sharp=20, max_surface_flat=4, surface_curvature_threshold=0.1, downsample_less_flat_features=0)
 EXTRACT_LOAM_FEATURES_ARGTYPES = [C.c_int, C.c_int32, _ip, _dp, _ip, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_double, C.c_int32, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _ip, _dp, _ip, _dp]
+#: bsgpu_build_registration_maps: the cap, the device sort's tile (tests follow it), the merge-only sentinel, the cell range and the
+#: typed prototype
+MAP_MAX_POINTS, MAP_SORT_TILE, MAP_MERGE_ONLY, MAP_CELL_RANGE = 8388608, 1024, -1.0, 1048576
+BUILD_REGISTRATION_MAPS_ARGTYPES = [C.c_int, C.c_int32, _ip, _ip, _dp, _dp, C.c_double, _ip, _dp, _ip]
 #: bsgpu_scan_context_describe / bsgpu_scan_context_match: the descriptor's shape, the limits, the reference's shipped parameters
 #: (SCManager's LIDAR_HEIGHT, PC_MAX_RADIUS, NUM_CANDIDATES_FROM_TREE, SEARCH_RATIO, SC_DIST_THRES, recalled) and the typed prototypes
 SC_RINGS, SC_SECTORS, SC_MAX_CANDIDATES, SC_MAX_TREE_CANDIDATES, SC_MAX_SCAN_POINTS = 20, 60, 65536, 64, 65535 * 4096

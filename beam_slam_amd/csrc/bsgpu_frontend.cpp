@@ -1,6 +1,6 @@
 // The front-end entry points of the C-ABI (include/bsgpu.h): bsgpu_preintegrate, bsgpu_inertial_alignment, bsgpu_register_scans,
-// bsgpu_register_scans_gicp, bsgpu_register_scans_loam, bsgpu_extract_loam_features, bsgpu_scan_context_describe, bsgpu_scan_context_match, bsgpu_triangulate, bsgpu_localize_frames and the three RANSACs.  Each checks its arguments, describes its arrays as a StageLayout (staging.h:
-// [inputs | outputs | scratch] in one device allocation), runs one kernel between one copy in and one copy out, and hands the
+// bsgpu_register_scans_gicp, bsgpu_register_scans_loam, bsgpu_extract_loam_features, bsgpu_build_registration_maps, bsgpu_scan_context_describe, bsgpu_scan_context_match, bsgpu_triangulate, bsgpu_localize_frames and the three RANSACs.  Each checks its arguments, describes its arrays as a StageLayout (staging.h:
+// [inputs | outputs | scratch] in one device allocation), runs its kernels between one copy in and one copy out, and hands the
 // results to the caller's arrays: nothing is written to them unless the call succeeds.
 #include <algorithm>
 #include <cmath>
@@ -13,6 +13,7 @@
 #include "inertial_align.h"
 #include "loam.h"
 #include "loam_features.h"
+#include "registration_map.h"
 #include "scan_context.h"
 #include "staging.h"
 
@@ -512,6 +513,82 @@ int bsgpu_extract_loam_features(int device, int32_t n_scans, const int32_t* scan
   return BSGPU_OK;
 } catch (...) {
   try { g_register_scans_error = "extract_loam_features: out of host memory"; } catch (...) {}
+  return api_exception(nullptr);
+}
+
+int bsgpu_build_registration_maps(int device, int32_t n_maps, const int32_t* map_scan_start, const int32_t* scan_start, const double* points,
+                                  const double* T_map_scan, double voxel_size, int32_t* map_start, double* map_points, int32_t* map_count) try {
+  const char* const me = "build_registration_maps";
+  const auto refuse = [me](int code, const char* why) { return refuse_scans(code, me, why); };
+  static_assert(BSGPU_MAP_MAX_POINTS == kMapMaxPoints && BSGPU_MAP_SORT_TILE == kMapSortTile, "the header's constants are registration_map.h's");
+  if (n_maps < 0 || !map_scan_start || !scan_start || !map_start || !map_points) return refuse(BSGPU_ERR_INVALID, "null argument");
+  if (!(voxel_size == kMapMergeOnly) && !(voxel_size > 0.0 && std::isfinite(voxel_size)))
+    return refuse(BSGPU_ERR_INVALID, "voxel_size must be -1 (merge only) or positive and finite");
+  switch (check_start_table(map_scan_start, n_maps)) {
+    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "map_scan_start[0] must be 0");
+    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "map_scan_start must be non-decreasing");
+    default: break;
+  }
+  const int32_t n_scans = map_scan_start[n_maps];
+  switch (check_start_table(scan_start, n_scans, INT_MAX, [&](int k) { return scan_start[k + 1] == scan_start[k] || points; })) {
+    case kStartNotZero: return refuse(BSGPU_ERR_INVALID, "scan_start[0] must be 0");
+    case kStartDecreasing: return refuse(BSGPU_ERR_INVALID, "scan_start must be non-decreasing");
+    case kStartBadItem: return refuse(BSGPU_ERR_INVALID, "null points");
+    default: break;
+  }
+  if (T_map_scan)
+    for (size_t i = 0; i < 12 * (size_t)n_scans; ++i) if (!std::isfinite(T_map_scan[i])) return refuse(BSGPU_ERR_INVALID, "non-finite T_map_scan");
+  if (scan_start[n_scans] > BSGPU_MAP_MAX_POINTS) return refuse(BSGPU_ERR_UNSUPPORTED, "the call holds more than BSGPU_MAP_MAX_POINTS points");
+  if (n_maps == 0) return BSGPU_OK;
+  const size_t nm = (size_t)n_maps, ns = (size_t)n_scans, np = (size_t)scan_start[n_scans];
+  if (np == 0) {
+    std::fill(map_start, map_start + nm + 1, 0);
+    return BSGPU_OK;
+  }
+  if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "hipSetDevice failed"); }
+  // a map's points are one range of the call's; its tiles of kMapSortTile positions follow those of the maps before it
+  std::vector<int32_t> pt_start(nm + 1), tile_start(nm + 1, 0), tile_map;
+  for (size_t m = 0; m <= nm; ++m) pt_start[m] = scan_start[map_scan_start[m]];
+  for (size_t m = 0; m < nm; ++m) {
+    const int32_t tiles = (pt_start[m + 1] - pt_start[m] + kMapSortTile - 1) / kMapSortTile;
+    tile_start[m + 1] = tile_start[m] + tiles;
+    tile_map.insert(tile_map.end(), (size_t)tiles, (int32_t)m);
+  }
+  const size_t nt = tile_map.size();
+  const bool sorted = voxel_size != kMapMergeOnly;
+  StageLayout L;
+  const int s_ss = L.in(scan_start, 4 * (ns + 1)), s_pts = L.in(points, 24 * np), s_T = L.in(T_map_scan, T_map_scan ? 96 * ns : 0),
+            s_ps = L.in(pt_start.data(), 4 * (nm + 1)), s_ts = L.in(tile_start.data(), 4 * (nm + 1)), s_tm = L.in(tile_map.data(), 4 * nt);
+  // fixed capacity: map m's voxels from the position of its first input point; the host packs below
+  const int s_op = L.out(nullptr, 24 * np), s_oc = L.out(nullptr, 4 * np), s_nv = L.out(nullptr, 4 * nm), s_rf = L.out(nullptr, 4);
+  const size_t sn = sorted ? np : 0, st = sorted ? nt : 0;
+  const int s_tq = L.scratch(24 * sn), s_ka = L.scratch(8 * sn), s_kb = L.scratch(8 * sn), s_ia = L.scratch(4 * sn), s_ib = L.scratch(4 * sn),
+            s_h = L.scratch(4 * 256 * st), s_th = L.scratch(4 * st);
+  DeviceStage D(L);
+  if (!D) return refuse(BSGPU_ERR_DEVICE, "out of device memory");
+  const auto I = [&](int s) { return D.ptr<int>(s); };
+  const hipError_t e = D.run(nullptr, [&] {
+    launch_build_registration_maps(nullptr, n_maps, n_scans, (int)np, (int)nt, I(s_ss), D.ptr<double>(s_pts), T_map_scan ? D.ptr<double>(s_T) : nullptr,
+                                   voxel_size, I(s_ps), I(s_ts), I(s_tm), D.ptr<double>(s_tq), D.ptr<unsigned long long>(s_ka),
+                                   D.ptr<unsigned long long>(s_kb), I(s_ia), I(s_ib), I(s_h), I(s_th), D.ptr<double>(s_op), I(s_oc), I(s_nv), I(s_rf));
+  });
+  if (e != hipSuccess) { (void)hipGetLastError(); return refuse(BSGPU_ERR_DEVICE, "device error"); }
+  if (*L.out_image<int32_t>(s_rf) != 0) return refuse(BSGPU_ERR_UNSUPPORTED, "a transformed coordinate has |q / voxel_size| >= 2^20");
+  const double* op = L.out_image<double>(s_op);
+  const int32_t *oc = L.out_image<int32_t>(s_oc), *nv = L.out_image<int32_t>(s_nv);
+  for (size_t m = 0; m < nm; ++m) if (nv[m] < 0 || nv[m] > pt_start[m + 1] - pt_start[m]) return refuse(BSGPU_ERR_DEVICE, "device error");
+  map_start[0] = 0;
+  for (size_t m = 0; m < nm; ++m) {
+    const size_t at = (size_t)map_start[m], from = (size_t)pt_start[m], k = (size_t)nv[m];
+    if (k) {
+      std::memcpy(map_points + 3 * at, op + 3 * from, 24 * k);
+      if (map_count) std::memcpy(map_count + at, oc + from, 4 * k);
+    }
+    map_start[m + 1] = (int32_t)(at + k);
+  }
+  return BSGPU_OK;
+} catch (...) {
+  try { g_register_scans_error = "build_registration_maps: out of host memory"; } catch (...) {}
   return api_exception(nullptr);
 }
 

@@ -599,6 +599,15 @@ struct LoamFeatParams;
 void launch_extract_loam_features(hipStream_t s, int n_scans, int n_points, const int* scan_start, const double* points, const int* ring,
                                   const LoamFeatParams& P, const double* bound, int pick_cap, int* ring_id, int* label, double* curvature,
                                   int* picks, int* counts, int* overflow);
+// The registration maps (k_registration_map.hip, bsgpu_build_registration_maps).  Inputs as the C-ABI's, on the device, plus what the host
+// derives: pt_start (n_maps + 1: a map's first point), tile_start (n_maps + 1: a map's first tile of kMapSortTile positions), tile_map
+// (n_tiles: a tile's map).  Scratch (read only when v is a voxel size): tq 3 per point, key_a / key_b and idx_a / idx_b 1 per point,
+// hist 256 per tile, tile_heads 1 per tile.  Out: out_pts 3 and out_cnt 1 per point (map m's voxels from pt_start[m]), n_vox per map,
+// range_flag (one int, cleared first): set when a finite coordinate has |q / v| >= 2^20.
+void launch_build_registration_maps(hipStream_t s, int n_maps, int n_scans, int n_points, int n_tiles, const int* scan_start, const double* points,
+                                    const double* T, double v, const int* pt_start, const int* tile_start, const int* tile_map, double* tq,
+                                    unsigned long long* key_a, unsigned long long* key_b, int* idx_a, int* idx_b, int* hist, int* tile_heads,
+                                    double* out_pts, int* out_cnt, int* n_vox, int* range_flag);
 // Scan Context place recognition (k_scan_context.hip, bsgpu_scan_context_describe / _match).  Inputs as the C-ABI's, on the device, plus
 // what the host derives: member_agg (a member's aggregate), max_chunks (chunks of kScChunk points of the longest scan a member names),
 // query_set (a query's set), pair_start (n_queries: where a query's (query, candidate) entries begin), R (the refinement radius).

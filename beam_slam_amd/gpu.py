@@ -283,6 +283,41 @@ def extract_loam_features(scan_start, points, ring=None, weak=True, labels=True,
     return out
 
 
+def build_registration_maps(map_scan_start, scan_start, points, T_map_scan=None, voxel_size=0.1, counts=True, device=0):
+    """bsgpu_build_registration_maps: the reference clouds of scan-to-map registration (RegistrationMap::GetLoamCloudMap /
+    GetPointCloudMap) for a batch of maps.  Map m owns scans map_scan_start[m]:map_scan_start[m+1], scan s is
+    points[scan_start[s]:scan_start[s+1]] in its own frame, T_map_scan (optional) is 3 x 4 per scan; voxel_size capi.MAP_MERGE_ONLY
+    merges only.  Returns a dict: map_start, map_points (the ref_*_start / ref_* arrays of register_scans_loam) and, with counts,
+    map_count."""
+    import numpy as np
+    ms = np.ascontiguousarray(map_scan_start, np.int32).reshape(-1)
+    ss = np.ascontiguousarray(scan_start, np.int32).reshape(-1)
+    pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+    T = None if T_map_scan is None else np.ascontiguousarray(T_map_scan, np.float64).reshape(-1, 12)
+    M = ms.size - 1
+    if M < 0 or ss.size < 1 or (M > 0 and int(ms.max()) > ss.size - 1) or (T is not None and T.shape[0] != ss.size - 1):
+        raise capi.SolverError(capi.ERR_INVALID, "build_registration_maps: array sizes do not agree")
+    if int(ss.max()) > pts.shape[0]:
+        raise capi.SolverError(capi.ERR_INVALID, "build_registration_maps: scan_start names more points than were passed")
+    n = pts.shape[0]
+    out = dict(map_start=np.zeros(M + 1, np.int32), map_points=np.zeros((n, 3)))
+    if counts:
+        out["map_count"] = np.zeros(n, np.int32)
+    fn = lib().bsgpu_build_registration_maps
+    fn.argtypes = capi.BUILD_REGISTRATION_MAPS_ARGTYPES
+    _dp, _ip = capi._dp, capi._ip
+    d = lambda x: None if x is None else x.ctypes.data_as(_dp)
+    i = lambda x: None if x is None else x.ctypes.data_as(_ip)
+    rc = fn(device, M, i(ms), i(ss), d(pts), d(T), float(voxel_size), i(out["map_start"]), d(out["map_points"]), i(out.get("map_count")))
+    if rc != 0:
+        raise capi.SolverError(rc, register_scans_error())
+    m = int(out["map_start"][-1]) if M > 0 else 0
+    out["map_points"] = out["map_points"][:m]
+    if counts:
+        out["map_count"] = out["map_count"][:m]
+    return out
+
+
 def register_scans_error():
     """What this thread's last failed bsgpu_register_scans objected to."""
     fn = lib().bsgpu_register_scans_error

@@ -3,7 +3,8 @@
 // matcher configuration (config/global_map/reloc_candidate_search_scan_context.json:6 -> matchers/gicp.json), around ONE
 // bsgpu_register_scans_gicp call:
 //   * input: the ranked match pairs of reloc_candidate_search.h (RelocResult::pairs, ascending Scan Context distance), per pair the two
-//     aggregated scans — ALREADY filtered: the voxel filter of :225-230 and the matcher's own res stay with the caller — and the four
+//     aggregated scans — ALREADY filtered: the voxel filter of :225-230 and the matcher's own res stay with the caller, who can have
+//     them from bsgpu_build_registration_maps (one map per aggregate, the scans under their T_ScanCenter_Scan) — and the four
 //     transforms of :194-197;
 //   * T_Candidate_Query_Init = inv(T_SubmapCandidate_Lidar) inv(T_World_CandidateSubmap) T_World_QuerySubmap T_SubmapQuery_Lidar
 //     (:234-238) goes to the device as T_init: ref = the candidate's scan, target = the query's (:243-244);

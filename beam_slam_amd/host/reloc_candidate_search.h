@@ -14,7 +14,8 @@
 //     aggregated scan, target = the query's, T_init = T_Candidate_Query_Init = inv(T_SubmapCandidate_Lidar) inv(T_World_CandidateSubmap)
 //     T_World_QuerySubmap T_SubmapQuery_Lidar (:234-238); T_CandidateSubmap_QuerySubmap = T_SubmapCandidate_Lidar T_Candidate_Query
 //     inv(T_SubmapQuery_Lidar) (:254-256).  The first converged pair in order is taken (:194-206).
-// Not here: the voxel filter of :225-230 stays with the caller (pass filtered clouds); the shipped matcher of this search is
+// Not here: the voxel filter of :225-230 stays with the caller (pass filtered clouds; bsgpu_build_registration_maps, one map per
+// aggregate, is the library's voxel filter: host/registration_map.h); the shipped matcher of this search is
 // matchers/gicp.json, which the device does not have — ICP (bsgpu_register_scans) is what it has.  Nothing is described,
 // matched or registered on the host: without the entry points in the back-end, or when a call fails, nothing is matched.
 #pragma once

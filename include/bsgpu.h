@@ -584,7 +584,8 @@ const char* bsgpu_register_scans_error(void);
  * GicpMatcher and PCL's GeneralizedIterativeClosestPoint are not in the reference checkout: what is taken from them below (the
  * covariances, the correspondence rule, the objective, the outer criterion, the constructor's defaults) is RECALLED, not verified, and
  * everything is computed in FP64.  PCL's GICP loop does not read fit_eps (recalled), so it is no parameter.  res, the matcher's voxel
- * downsampling, is the caller's job: the clouds are registered as they are passed.
+ * downsampling, is the caller's job: the clouds are registered as they are passed (bsgpu_build_registration_maps is the library's
+ * voxel filter).
  * Clouds and roles as in bsgpu_register_scans: S the reference cloud (SetRef, PCL's source), Q the target cloud after T_init (optional,
  * 12 doubles per pair, row-major 3 x 4; NULL: the identity) has been applied to it on the device.
  *   covariances       (PCL's computeCovariances) once per cloud per call.  For a point p of a cloud P, |P| >= k_neighbors = k: its k
@@ -634,7 +635,8 @@ int bsgpu_register_scans_gicp(int device, int32_t n_pairs, const int32_t* ref_st
  * 158-188), RelocRefinementLoamRegistration (reloc_refinement_loam_registration.cpp:91-118), submap_alignment.cpp:76-96 and
  * global_map_batch_optimization.cpp:238-247 in the shipped configuration (config/matchers/loam_*.json, optimization/ceres_config.json).
  * The matcher's boundary is kept: LoamPointCloud in, transform and covariance out; feature extraction (LoamFeatureExtractor) is a
- * separate step: bsgpu_extract_loam_features, below.  [EXT] libbeam's LoamMatcher, LoamScanRegistration, CeresPointToLineCostFunction and
+ * separate step: bsgpu_extract_loam_features, below; the scan-to-map reference clouds (RegistrationMap::GetLoamCloudMap) come from
+ * bsgpu_build_registration_maps, further below.  [EXT] libbeam's LoamMatcher, LoamScanRegistration, CeresPointToLineCostFunction and
  * CeresPointToPlaneCostFunction are not in the reference checkout: everything below is RECALLED, not verified, and where the text says
  * "the library's choice" this library decides something the recollection leaves open.
  *   clouds            pair p has four packed-xyz clouds, start tables as in bsgpu_register_scans: the reference's edge and surface
@@ -743,7 +745,8 @@ int bsgpu_register_scans_loam(int device, int32_t n_pairs, const int32_t* ref_ed
  * depends on how the device schedules its lanes.  One workgroup per (scan, ring): a lone revolution uses as many compute units as it
  * has rings.
  * OUT OF SCOPE: the voxel filter of the weak surfaces (downsample_less_flat_features must be 0), deskewing, intensity and time fields,
- * and keeping the features on the device for the matcher: the two calls are chained through host arrays.
+ * and keeping the features on the device for the matcher: the two calls are chained through host arrays.  The map of the registered
+ * scans' features that a scan-to-map matcher reads is bsgpu_build_registration_maps, below.
  * INVALID: NULL where an array is needed, a weak group given in part, everything bsgpu_register_scans refuses of a start table,
  * number_of_beams, n_feature_regions or curvature_region < 1, a negative count, fov_deg not in (0, 180), a threshold that is not
  * finite, an unknown vertical_axis.  UNSUPPORTED: number_of_beams > BSGPU_LOAM_MAX_RINGS, a ring of more than
@@ -763,6 +766,49 @@ int bsgpu_extract_loam_features(int device, int32_t n_scans, const int32_t* scan
                                 int32_t* edge_index, double* edge_points, int32_t* surf_start, int32_t* surf_index, double* surf_points,
                                 int32_t* weak_edge_start, int32_t* weak_edge_index, double* weak_edge_points, int32_t* weak_surf_start,
                                 int32_t* weak_surf_index, double* weak_surf_points, int32_t* label, double* curvature);
+
+/* Registration maps for a batch of maps — the reference clouds of scan-to-map registration: RegistrationMap::GetLoamCloudMap and
+ * GetPointCloudMap (bs_models/src/lib/scan_registration/registration_map.cpp:96-135), which ScanToMapLoamRegistration::RegisterScanToMap
+ * (scan_to_map_registration.cpp:168-197) rebuilds for every incoming scan from the last map_size registered scans (registration/
+ * scan_to_map.json: 45 scans, leaf 0.1 m), and the aggregates that Scan Context and GICP take (reloc_candidate_search_scan_context.cpp:
+ * 225-230, global_mapping/utils.cpp:27-43).  One primitive: transform, merge, voxel-reduce.  A "map" is ONE cloud class of one map: the
+ * LOAM map is two maps in one call (the scans' edge clouds, then their surface clouds), GetPointCloudMap is one, a batch of
+ * loop-closure aggregates one each.  [EXT] libbeam's VoxelDownsample and pcl::VoxelGrid are not in the reference checkout: everything
+ * below is RECALLED, not verified, and where the text says "the library's choice" this library decides something the recollection
+ * leaves open.  Arithmetic is FP64.
+ *   maps              map m owns scans [map_scan_start[m], map_scan_start[m+1]); scan s is points[3 scan_start[s] .. 3 scan_start[s+1]),
+ *                     packed xyz in its own (lidar) frame; the call has map_scan_start[n_maps] scans.  Start tables as in
+ *                     bsgpu_register_scans.
+ *   transform         every point goes through its scan's T_map_scan (12 doubles, row-major 3 x 4) by the fused multiply-adds of the
+ *                     scan registrations (point_grid.h: grid_apply).  T_map_scan == NULL: the identity, the points are taken as they are.
+ *   voxel             of a transformed point q: (floor(q.x / v), floor(q.y / v), floor(q.z / v)), v = voxel_size; the grid is anchored
+ *                     at the origin, as pcl::VoxelGrid anchors it.  A point exactly on a boundary belongs to the upper cell; negative
+ *                     coordinates floor, they do not truncate.
+ *   output            one point per occupied voxel: the sum of the voxel's transformed points IN INPUT ORDER (scan order, then point
+ *                     order), taken sequentially in FP64 from +0.0, divided by their number.
+ *   order             within a map ascending (iz, iy, ix): PCL's order of idx = ix' + iy' dx + iz' dx dy, whatever the bounding box.
+ *   non-finite        a point with a transformed coordinate that is not finite is dropped when voxel_size > 0.
+ *   merge only        voxel_size == -1 (the reference's sentinel): every transformed point is copied in input order, map_count is 1.
+ *   stateless         a scan is passed in its own frame with its current T_Map_Scan on every call: the library's choice.  The reference
+ *                     stores transformed float clouds and, in UpdateScan, re-transforms them incrementally.
+ *   NOT MODELLED      min_points_per_voxel, PCL's float accumulation and inverse_leaf multiply, and libbeam's splitting of a cloud whose
+ *                     PCL index would overflow an int (the 63-bit key here — 21 biased bits per axis, iz most significant — has no such
+ *                     overflow).
+ * Outputs: map_start (n_maps + 1) and map_points (packed xyz; capacity 3 x the call's points) are exactly the layout
+ * bsgpu_register_scans_loam takes for ref_edge_start / ref_edges and ref_surf_start / ref_surfs, and bsgpu_register_scans_gicp for its
+ * clouds.  map_count (optional, capacity the call's points): input points per output point.
+ * n_maps == 0 does nothing; a map without points gives an empty range.  A map's bytes depend neither on its neighbours in the call nor
+ * on how the device schedules its lanes: the device sorts (key, index) with a stable radix sort inside each map and sums a voxel's run
+ * sequentially; there are no floating-point atomics.
+ * INVALID: NULL map_scan_start, scan_start, map_start or map_points, NULL points where a scan has some, everything
+ * bsgpu_register_scans refuses of a start table (either one), voxel_size neither -1 nor positive and finite, a non-finite entry of
+ * T_map_scan.  UNSUPPORTED: more than BSGPU_MAP_MAX_POINTS points in the call; a finite transformed coordinate with
+ * |q / voxel_size| >= 2^20 (the device reports it through a flag that is only ever set to 1).  Nothing is written unless the call
+ * succeeds; bsgpu_register_scans_error says what this thread's last failed call objected to, prefixed "build_registration_maps: ".  */
+#define BSGPU_MAP_MAX_POINTS 8388608
+#define BSGPU_MAP_SORT_TILE 1024      /* keys per workgroup of the device's sort; no output depends on it */
+int bsgpu_build_registration_maps(int device, int32_t n_maps, const int32_t* map_scan_start, const int32_t* scan_start, const double* points,
+                                  const double* T_map_scan, double voxel_size, int32_t* map_start, double* map_points, int32_t* map_count);
 
 /* Scan Context place recognition — the descriptors and the search of RelocCandidateSearchScanContext::FindRelocCandidates
  * (bs_models/src/lib/reloc/reloc_candidate_search_scan_context.cpp:117-150): the step that decides which scan pairs
