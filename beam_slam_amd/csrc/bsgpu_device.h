@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "../../include/bsgpu.h"
 #include "bsgpu_internal.h"
 #include "lm_decide.h"
@@ -10,6 +12,25 @@
 namespace bsg {
 
 #define BSG_DEV __device__ __forceinline__
+
+// An entry of a `_batch` kernel's argument table (BatchArgTable) is declared once, as `template <template <class> class P> struct X_ArgsT`,
+// with P giving the kind of its pointer fields: X_ArgsT<AsPassed> (= X_Args) is what the host fills and BatchArgTable::push copies,
+// X_ArgsT<AsRead> is the same bytes as the kernel reads them.  Structs nested in an entry keep generic pointers under both.
+template <class T> using AsPassed = T*;
+template <class T> using AsRead = T __attribute__((address_space(1)))*;
+// Entry w of a table, its pointers GLOBAL pointers.  Pointers read from memory are generic ones: every load through them would be a FLAT
+// instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic (the pair kernel
+// ran 1.9x slower per window).  The entry is read in place, by reference: copied into a local struct its dynamically indexed members went
+// to scratch (DESIGN.md "N windows advanced by ONE set of launches").
+template <template <template <class> class> class X>
+BSG_DEV const X<AsRead>& batch_entry(const X<AsPassed>* table, int w) {
+  static_assert(sizeof(X<AsRead>) == sizeof(X<AsPassed>) && alignof(X<AsRead>) == alignof(X<AsPassed>), "both views of an entry have one layout");
+  static_assert(std::is_trivially_copyable<X<AsPassed>>::value && std::is_trivially_copyable<X<AsRead>>::value, "BatchArgTable::push copies the entry with memcpy");
+  return reinterpret_cast<const X<AsRead>*>(table)[w];
+}
+// a field of such an entry as the `_body` functions take it: the generic pointer to the same pointee type
+template <class T>
+BSG_DEV T* generic(T __attribute__((address_space(1)))* p) { return (T*)p; }
 
 // entry (row rw, pose column j: theta 0..2, t 3..5) of factor f's pose part of the reprojection Jacobian under either layout (Visual::ja; the
 // compact one keeps no t columns: they are the negated landmark part) — for the readers off the hot path

@@ -366,79 +366,51 @@ __global__ __launch_bounds__(kBandThreads) void pairs_band_nocr_kernel(int n_uni
   pairs_band_kernel_body<true, COMPACT>((int)blockIdx.x, (int)gridDim.x, n_units, unit_start, unit_cam, band_lm, n_cam_pose, J, r, JB, cp_tq, cp_tp, S, ld, rhs_row, grad, hdiag, perm, grad_only, small, n_small_units, lm_id, Linv, z);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
-struct pairs_band_kernel_Args {
+template <template <class> class P>
+struct pairs_band_kernel_ArgsT {
   int bsg_grid;
   int n_units;
-  const int* unit_start;
-  const int* unit_cam;
-  const int4* band_lm;
+  P<const int> unit_start;
+  P<const int> unit_cam;
+  P<const int4> band_lm;
   int n_cam_pose;
-  const double* J;
-  const double2* r;
-  const double* CR;
-  const int* cp_tq;
-  const int* cp_tp;
-  double* S;
+  P<const double> J;
+  P<const double2> r;
+  P<const double> CR;
+  P<const int> cp_tq;
+  P<const int> cp_tp;
+  P<double> S;
   int ld;
   int rhs_row;
-  double* grad;
-  double* hdiag;
-  const int* perm;
+  P<double> grad;
+  P<double> hdiag;
+  P<const int> perm;
   int grad_only;
   SmallGroupSet small;
   int n_small_units;
   // (Visual::no_cr — all null otherwise: the landmark parts of the Jacobian rows, the band records' landmarks, their Linv | z records)
-  const double* JB;
-  const int* lm_id;
-  const double* Linv;
-  const double* z;
+  P<const double> JB;
+  P<const int> lm_id;
+  P<const double> Linv;
+  P<const double> z;
   int ja;   // (Visual::ja: the pitch of J's pose part)
 };
-// (the same entry as the kernel reads it: its pointers are GLOBAL pointers — read as generic ones every load through them would be a FLAT
-// instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic)
-struct pairs_band_kernel_ArgsG {
-  int bsg_grid;
-  int n_units;
-  const int __attribute__((address_space(1)))* unit_start;
-  const int __attribute__((address_space(1)))* unit_cam;
-  const int4 __attribute__((address_space(1)))* band_lm;
-  int n_cam_pose;
-  const double __attribute__((address_space(1)))* J;
-  const double2 __attribute__((address_space(1)))* r;
-  const double __attribute__((address_space(1)))* CR;
-  const int __attribute__((address_space(1)))* cp_tq;
-  const int __attribute__((address_space(1)))* cp_tp;
-  double __attribute__((address_space(1)))* S;
-  int ld;
-  int rhs_row;
-  double __attribute__((address_space(1)))* grad;
-  double __attribute__((address_space(1)))* hdiag;
-  const int __attribute__((address_space(1)))* perm;
-  int grad_only;
-  SmallGroupSet small;
-  int n_small_units;
-  const double __attribute__((address_space(1)))* JB;
-  const int __attribute__((address_space(1)))* lm_id;
-  const double __attribute__((address_space(1)))* Linv;
-  const double __attribute__((address_space(1)))* z;
-  int ja;
-};
-static_assert(sizeof(pairs_band_kernel_ArgsG) == sizeof(pairs_band_kernel_Args), "layout");
+using pairs_band_kernel_Args = pairs_band_kernel_ArgsT<AsPassed>;
 
 __global__ __launch_bounds__(kBandThreads) void pairs_band_kernel_batch(const pairs_band_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list) {
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.y];
-  const pairs_band_kernel_ArgsG& a = reinterpret_cast<const pairs_band_kernel_ArgsG*>(bsg_A)[bsg_w];
+  const pairs_band_kernel_ArgsT<AsRead>& a = batch_entry(bsg_A, bsg_w);
   if ((int)blockIdx.x >= a.bsg_grid) return;
   // (a batch's systems are read by the fused tiled factorisation next: the units add into the lower triangle only, as a lone step's do — bit 1;
   //  a window's gradient-only step adds no tiles at all)
   const int band_mode = bsg_dyn->grad_only[bsg_w] ? 1 : 2;
   // (a window without C rows — Visual::no_cr — forms them from B, Linv and z as its lone launch does)
   if (a.Linv && a.ja == kJACompact)
-    pairs_band_kernel_body<true, true>((int)blockIdx.x, a.bsg_grid, a.n_units, (const int*)a.unit_start, (const int*)a.unit_cam, (const int4*)a.band_lm, a.n_cam_pose, (const double*)a.J, (const double2*)a.r, (const double*)a.JB, (const int*)a.cp_tq, (const int*)a.cp_tp, (double*)a.S, a.ld, a.rhs_row, (double*)a.grad, (double*)a.hdiag, (const int*)a.perm, band_mode, a.small, a.n_small_units, (const int*)a.lm_id, (const double*)a.Linv, (const double*)a.z);
+    pairs_band_kernel_body<true, true>((int)blockIdx.x, a.bsg_grid, a.n_units, generic(a.unit_start), generic(a.unit_cam), generic(a.band_lm), a.n_cam_pose, generic(a.J), generic(a.r), generic(a.JB), generic(a.cp_tq), generic(a.cp_tp), generic(a.S), a.ld, a.rhs_row, generic(a.grad), generic(a.hdiag), generic(a.perm), band_mode, a.small, a.n_small_units, generic(a.lm_id), generic(a.Linv), generic(a.z));
   else if (a.Linv)
-    pairs_band_kernel_body<true>((int)blockIdx.x, a.bsg_grid, a.n_units, (const int*)a.unit_start, (const int*)a.unit_cam, (const int4*)a.band_lm, a.n_cam_pose, (const double*)a.J, (const double2*)a.r, (const double*)a.JB, (const int*)a.cp_tq, (const int*)a.cp_tp, (double*)a.S, a.ld, a.rhs_row, (double*)a.grad, (double*)a.hdiag, (const int*)a.perm, band_mode, a.small, a.n_small_units, (const int*)a.lm_id, (const double*)a.Linv, (const double*)a.z);
+    pairs_band_kernel_body<true>((int)blockIdx.x, a.bsg_grid, a.n_units, generic(a.unit_start), generic(a.unit_cam), generic(a.band_lm), a.n_cam_pose, generic(a.J), generic(a.r), generic(a.JB), generic(a.cp_tq), generic(a.cp_tp), generic(a.S), a.ld, a.rhs_row, generic(a.grad), generic(a.hdiag), generic(a.perm), band_mode, a.small, a.n_small_units, generic(a.lm_id), generic(a.Linv), generic(a.z));
   else
-  pairs_band_kernel_body((int)blockIdx.x, a.bsg_grid, a.n_units, (const int*)a.unit_start, (const int*)a.unit_cam, (const int4*)a.band_lm, a.n_cam_pose, (const double*)a.J, (const double2*)a.r, (const double*)a.CR, (const int*)a.cp_tq, (const int*)a.cp_tp, (double*)a.S, a.ld, a.rhs_row, (double*)a.grad, (double*)a.hdiag, (const int*)a.perm, band_mode, a.small, a.n_small_units);
+  pairs_band_kernel_body((int)blockIdx.x, a.bsg_grid, a.n_units, generic(a.unit_start), generic(a.unit_cam), generic(a.band_lm), a.n_cam_pose, generic(a.J), generic(a.r), generic(a.CR), generic(a.cp_tq), generic(a.cp_tp), generic(a.S), a.ld, a.rhs_row, generic(a.grad), generic(a.hdiag), generic(a.perm), band_mode, a.small, a.n_small_units);
 }
 
 // The band kernels need kBandLds (~147 KB) of dynamic LDS per workgroup: the opt-in is made once per device (keyed by the whole device id)

@@ -1366,58 +1366,38 @@ __global__ __launch_bounds__(kFusedThreads) void chol_fused_kernel(double* __res
   chol_fused_kernel_body<PROBE>((int)blockIdx.x, (int)gridDim.x, S, Lp, ld, tasks, n_tasks, tile_tot, nreal, Vinv, scal, sync, Winv, fs, rhs_strips, diag, gn, probe_ts);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
-struct chol_fused_kernel_Args {
+template <template <class> class P>
+struct chol_fused_kernel_ArgsT {
   int bsg_grid;
-  double* S;
-  double* Lp;
+  P<double> S;
+  P<double> Lp;
   int ld;
-  const FusedTask* tasks;
+  P<const FusedTask> tasks;
   int n_tasks;
-  const int* tile_tot;
-  const int* nreal;
-  double* Vinv;
-  double* scal;
-  int* sync;
-  double* Winv;
+  P<const int> tile_tot;
+  P<const int> nreal;
+  P<double> Vinv;
+  P<double> scal;
+  P<int> sync;
+  P<double> Winv;
   int fs;
   int rhs_strips;
-  long long* probe_ts;
+  P<long long> probe_ts;
   LmDiag diag;        // (radius and the step's flags: per round, BatchDyn)
   GradNormRide gn;
 };
-// (the same entry as the kernel reads it: its pointers are GLOBAL pointers — read as generic ones every load through them would be a FLAT
-// instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic)
-struct chol_fused_kernel_ArgsG {
-  int bsg_grid;
-  double __attribute__((address_space(1)))* S;
-  double __attribute__((address_space(1)))* Lp;
-  int ld;
-  const FusedTask __attribute__((address_space(1)))* tasks;
-  int n_tasks;
-  const int __attribute__((address_space(1)))* tile_tot;
-  const int __attribute__((address_space(1)))* nreal;
-  double __attribute__((address_space(1)))* Vinv;
-  double __attribute__((address_space(1)))* scal;
-  int __attribute__((address_space(1)))* sync;
-  double __attribute__((address_space(1)))* Winv;
-  int fs;
-  int rhs_strips;
-  long long __attribute__((address_space(1)))* probe_ts;
-  LmDiag diag;
-  GradNormRide gn;
-};
-static_assert(sizeof(chol_fused_kernel_ArgsG) == sizeof(chol_fused_kernel_Args), "layout");
+using chol_fused_kernel_Args = chol_fused_kernel_ArgsT<AsPassed>;
 
 template <bool PROBE>
 __global__ __launch_bounds__(kFusedThreads) void chol_fused_kernel_batch(const chol_fused_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list) {
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.x];
-  const chol_fused_kernel_ArgsG& a = reinterpret_cast<const chol_fused_kernel_ArgsG*>(bsg_A)[bsg_w];
+  const chol_fused_kernel_ArgsT<AsRead>& a = batch_entry(bsg_A, bsg_w);
   if ((int)blockIdx.y >= a.bsg_grid) return;   // (windows interleaved in dispatch order: x = window, y = the window's workgroup — the workgroups of ALL windows take their tickets side by side)
   LmDiag diag = a.diag;   // (small: patched copies; the rest of the entry is read in place)
   diag.inv_radius = 1.0 / bsg_dyn->radius[bsg_w]; diag.compute_scale = bsg_dyn->first[bsg_w]; diag.compute_dcl = bsg_dyn->new_J[bsg_w];
   GradNormRide gn = a.gn;
   if (!bsg_dyn->new_J[bsg_w]) gn.nb = 0;
-  chol_fused_kernel_body<PROBE>((int)blockIdx.y, a.bsg_grid, (double*)a.S, (double*)a.Lp, a.ld, (const FusedTask*)a.tasks, a.n_tasks, (const int*)a.tile_tot, (const int*)a.nreal, (double*)a.Vinv, (double*)a.scal, (int*)a.sync, (double*)a.Winv, a.fs, a.rhs_strips, diag, gn, (long long*)a.probe_ts);
+  chol_fused_kernel_body<PROBE>((int)blockIdx.y, a.bsg_grid, generic(a.S), generic(a.Lp), a.ld, generic(a.tasks), a.n_tasks, generic(a.tile_tot), generic(a.nreal), generic(a.Vinv), generic(a.scal), generic(a.sync), generic(a.Winv), a.fs, a.rhs_strips, diag, gn, generic(a.probe_ts));
 }
 // ints between two words of the sync area: 16 = a 64-byte line each (packed words of one line that different workgroups write are
 // serialised at the memory side: 270 -> 237 us per C2 factorisation when they were moved apart, round 2)
@@ -1742,54 +1722,34 @@ __global__ __launch_bounds__(1024) void chol_backsolve_chain_kernel(const double
   chol_backsolve_chain_kernel_body<Y_IN_LDS, CH, DEEP, USE_W>((int)blockIdx.x, (int)gridDim.x, S, Lp, Vinv, ld, bs_desc, chain_begin, chain_end, rows_flat, y, npad, max_len, y_init, iperm, n_pose, y_tan, delta);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
-struct chol_backsolve_chain_kernel_Args {
+template <template <class> class P>
+struct chol_backsolve_chain_kernel_ArgsT {
   int bsg_grid;
-  const double* S;
-  const double* Lp;
-  const double* Vinv;
+  P<const double> S;
+  P<const double> Lp;
+  P<const double> Vinv;
   int ld;
-  const int* bs_desc;
-  const int* chain_begin;
-  const int* chain_end;
-  const int* rows_flat;
-  double* y;
+  P<const int> bs_desc;
+  P<const int> chain_begin;
+  P<const int> chain_end;
+  P<const int> rows_flat;
+  P<double> y;
   int npad;
   int max_len;
-  const double* y_init;
-  const int* iperm;
+  P<const double> y_init;
+  P<const int> iperm;
   int n_pose;
-  double* y_tan;
-  double* delta;
+  P<double> y_tan;
+  P<double> delta;
 };
-// (the same entry as the kernel reads it: its pointers are GLOBAL pointers — read as generic ones every load through them would be a FLAT
-// instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic)
-struct chol_backsolve_chain_kernel_ArgsG {
-  int bsg_grid;
-  const double __attribute__((address_space(1)))* S;
-  const double __attribute__((address_space(1)))* Lp;
-  const double __attribute__((address_space(1)))* Vinv;
-  int ld;
-  const int __attribute__((address_space(1)))* bs_desc;
-  const int __attribute__((address_space(1)))* chain_begin;
-  const int __attribute__((address_space(1)))* chain_end;
-  const int __attribute__((address_space(1)))* rows_flat;
-  double __attribute__((address_space(1)))* y;
-  int npad;
-  int max_len;
-  const double __attribute__((address_space(1)))* y_init;
-  const int __attribute__((address_space(1)))* iperm;
-  int n_pose;
-  double __attribute__((address_space(1)))* y_tan;
-  double __attribute__((address_space(1)))* delta;
-};
-static_assert(sizeof(chol_backsolve_chain_kernel_ArgsG) == sizeof(chol_backsolve_chain_kernel_Args), "layout");
+using chol_backsolve_chain_kernel_Args = chol_backsolve_chain_kernel_ArgsT<AsPassed>;
 
 template <bool Y_IN_LDS, int CH, bool DEEP, bool USE_W>
 __global__ __launch_bounds__(1024) void chol_backsolve_chain_kernel_batch(const chol_backsolve_chain_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list) {
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.x];
-  const chol_backsolve_chain_kernel_ArgsG& a = reinterpret_cast<const chol_backsolve_chain_kernel_ArgsG*>(bsg_A)[bsg_w];
+  const chol_backsolve_chain_kernel_ArgsT<AsRead>& a = batch_entry(bsg_A, bsg_w);
   if ((int)blockIdx.y >= a.bsg_grid) return;   // (windows interleaved in dispatch order: x = window, y = the window's workgroup — the workgroups of ALL windows take their tickets side by side)
-  chol_backsolve_chain_kernel_body<Y_IN_LDS, CH, DEEP, USE_W>((int)blockIdx.y, a.bsg_grid, (double*)a.S, (double*)a.Lp, (double*)a.Vinv, a.ld, (const int*)a.bs_desc, (const int*)a.chain_begin, (const int*)a.chain_end, (const int*)a.rows_flat, (double*)a.y, a.npad, a.max_len, (const double*)a.y_init, (const int*)a.iperm, a.n_pose, (double*)a.y_tan, (double*)a.delta);
+  chol_backsolve_chain_kernel_body<Y_IN_LDS, CH, DEEP, USE_W>((int)blockIdx.y, a.bsg_grid, generic(a.S), generic(a.Lp), generic(a.Vinv), a.ld, generic(a.bs_desc), generic(a.chain_begin), generic(a.chain_end), generic(a.rows_flat), generic(a.y), a.npad, a.max_len, generic(a.y_init), generic(a.iperm), a.n_pose, generic(a.y_tan), generic(a.delta));
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1911,78 +1871,46 @@ __global__ __launch_bounds__(1024) void chol_backsolve_fused_kernel(const double
   chol_backsolve_fused_kernel_body<CH, DEEP>((int)blockIdx.x, (int)gridDim.x, Lp, Winv, ld, bs_desc, chain_begin, chain_end, rows_flat, n_chains, chain_group, grp_nchains, grp_nitems, G, items, upd_rows, tile_updated, y, npad, max_len, y_init, iperm, n_pose, y_tan, delta, sync, scal, ts, order, fs);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
-struct chol_backsolve_fused_kernel_Args {
+template <template <class> class P>
+struct chol_backsolve_fused_kernel_ArgsT {
   int bsg_grid;
-  const double* Lp;
-  const double* Winv;
+  P<const double> Lp;
+  P<const double> Winv;
   int ld;
-  const int* bs_desc;
-  const int* chain_begin;
-  const int* chain_end;
-  const int* rows_flat;
+  P<const int> bs_desc;
+  P<const int> chain_begin;
+  P<const int> chain_end;
+  P<const int> rows_flat;
   int n_chains;
-  const int* chain_group;
-  const int* grp_nchains;
-  const int* grp_nitems;
+  P<const int> chain_group;
+  P<const int> grp_nchains;
+  P<const int> grp_nitems;
   int G;
-  const int* items;
-  const int* upd_rows;
-  const int* tile_updated;
-  double* y;
+  P<const int> items;
+  P<const int> upd_rows;
+  P<const int> tile_updated;
+  P<double> y;
   int npad;
   int max_len;
-  const double* y_init;
-  const int* iperm;
+  P<const double> y_init;
+  P<const int> iperm;
   int n_pose;
-  double* y_tan;
-  double* delta;
-  int* sync;
-  double* scal;
-  long long* ts;
-  const int* order;
+  P<double> y_tan;
+  P<double> delta;
+  P<int> sync;
+  P<double> scal;
+  P<long long> ts;
+  P<const int> order;
   int fs;
 };
-// (the same entry as the kernel reads it: its pointers are GLOBAL pointers — read as generic ones every load through them would be a FLAT
-// instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic)
-struct chol_backsolve_fused_kernel_ArgsG {
-  int bsg_grid;
-  const double __attribute__((address_space(1)))* Lp;
-  const double __attribute__((address_space(1)))* Winv;
-  int ld;
-  const int __attribute__((address_space(1)))* bs_desc;
-  const int __attribute__((address_space(1)))* chain_begin;
-  const int __attribute__((address_space(1)))* chain_end;
-  const int __attribute__((address_space(1)))* rows_flat;
-  int n_chains;
-  const int __attribute__((address_space(1)))* chain_group;
-  const int __attribute__((address_space(1)))* grp_nchains;
-  const int __attribute__((address_space(1)))* grp_nitems;
-  int G;
-  const int __attribute__((address_space(1)))* items;
-  const int __attribute__((address_space(1)))* upd_rows;
-  const int __attribute__((address_space(1)))* tile_updated;
-  double __attribute__((address_space(1)))* y;
-  int npad;
-  int max_len;
-  const double __attribute__((address_space(1)))* y_init;
-  const int __attribute__((address_space(1)))* iperm;
-  int n_pose;
-  double __attribute__((address_space(1)))* y_tan;
-  double __attribute__((address_space(1)))* delta;
-  int __attribute__((address_space(1)))* sync;
-  double __attribute__((address_space(1)))* scal;
-  long long __attribute__((address_space(1)))* ts;
-  const int __attribute__((address_space(1)))* order;
-  int fs;
-};
-static_assert(sizeof(chol_backsolve_fused_kernel_ArgsG) == sizeof(chol_backsolve_fused_kernel_Args), "layout");
+using chol_backsolve_fused_kernel_Args = chol_backsolve_fused_kernel_ArgsT<AsPassed>;
 
 template <int CH, bool DEEP>
 __global__ __launch_bounds__(1024) void chol_backsolve_fused_kernel_batch(const chol_backsolve_fused_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list) {
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.x];
-  const chol_backsolve_fused_kernel_ArgsG& a = reinterpret_cast<const chol_backsolve_fused_kernel_ArgsG*>(bsg_A)[bsg_w];
+  const chol_backsolve_fused_kernel_ArgsT<AsRead>& a = batch_entry(bsg_A, bsg_w);
   if ((int)blockIdx.y >= a.bsg_grid) return;   // (windows interleaved in dispatch order: x = window, y = the window's workgroup — the workgroups of ALL windows take their tickets side by side)
-  chol_backsolve_fused_kernel_body<CH, DEEP>((int)blockIdx.y, a.bsg_grid, (double*)a.Lp, (double*)a.Winv, a.ld, (const int*)a.bs_desc, (const int*)a.chain_begin, (const int*)a.chain_end, (const int*)a.rows_flat, a.n_chains, (const int*)a.chain_group, (const int*)a.grp_nchains, (const int*)a.grp_nitems, a.G, (const int*)a.items, (const int*)a.upd_rows, (const int*)a.tile_updated, (double*)a.y, a.npad, a.max_len, (const double*)a.y_init, (const int*)a.iperm, a.n_pose, (double*)a.y_tan, (double*)a.delta, (int*)a.sync, (double*)a.scal, (long long*)a.ts, (const int*)a.order, a.fs);
+  chol_backsolve_fused_kernel_body<CH, DEEP>((int)blockIdx.y, a.bsg_grid, generic(a.Lp), generic(a.Winv), a.ld, generic(a.bs_desc), generic(a.chain_begin), generic(a.chain_end), generic(a.rows_flat), a.n_chains, generic(a.chain_group), generic(a.grp_nchains), generic(a.grp_nitems), a.G, generic(a.items), generic(a.upd_rows), generic(a.tile_updated), generic(a.y), a.npad, a.max_len, generic(a.y_init), generic(a.iperm), a.n_pose, generic(a.y_tan), generic(a.delta), generic(a.sync), generic(a.scal), generic(a.ts), generic(a.order), a.fs);
 }
 // false: not launched (the grid would not be resident at once, or y does not fit LDS) — the caller takes the launch-per-level path
 bool launch_chol_backsolve_fused(hipStream_t s, const double* Lp, const double* Winv, int ld, const int* bs_desc_dev, const int* chain_begin_dev,

@@ -79,43 +79,30 @@ __global__ __launch_bounds__(256) void grad_norms_kernel(int nb, const int* __re
   grad_norms_kernel_body<WITH_DIAG>((int)blockIdx.x, (int)gridDim.x, nb, xoff, toff, size, manifold, x, grad, gpart, pd);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
-struct grad_norms_kernel_Args {
+template <template <class> class P>
+struct grad_norms_kernel_ArgsT {
   int bsg_grid;
   int nb;
-  const int* xoff;
-  const int* toff;
-  const unsigned char* size;
-  const unsigned char* manifold;
-  const double* x;
-  const double* grad;
-  double* gpart;
+  P<const int> xoff;
+  P<const int> toff;
+  P<const unsigned char> size;
+  P<const unsigned char> manifold;
+  P<const double> x;
+  P<const double> grad;
+  P<double> gpart;
   PoseDiagArgs pd;
 };
-// (the same entry as the kernel reads it: its pointers are GLOBAL pointers — read as generic ones every load through them would be a FLAT
-// instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic)
-struct grad_norms_kernel_ArgsG {
-  int bsg_grid;
-  int nb;
-  const int __attribute__((address_space(1)))* xoff;
-  const int __attribute__((address_space(1)))* toff;
-  const unsigned char __attribute__((address_space(1)))* size;
-  const unsigned char __attribute__((address_space(1)))* manifold;
-  const double __attribute__((address_space(1)))* x;
-  const double __attribute__((address_space(1)))* grad;
-  double __attribute__((address_space(1)))* gpart;
-  PoseDiagArgs pd;
-};
-static_assert(sizeof(grad_norms_kernel_ArgsG) == sizeof(grad_norms_kernel_Args), "layout");
+using grad_norms_kernel_Args = grad_norms_kernel_ArgsT<AsPassed>;
 
 template <bool WITH_DIAG>
 __global__ __launch_bounds__(256) void grad_norms_kernel_batch(const grad_norms_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list) {
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.y];
-  const grad_norms_kernel_ArgsG& a = reinterpret_cast<const grad_norms_kernel_ArgsG*>(bsg_A)[bsg_w];
+  const grad_norms_kernel_ArgsT<AsRead>& a = batch_entry(bsg_A, bsg_w);
   if ((int)blockIdx.x >= a.bsg_grid) return;
   PoseDiagArgs pd = a.pd;
   pd.radius_ptr = nullptr; pd.radius_val = bsg_dyn->radius[bsg_w];
   pd.compute_scale = bsg_dyn->first[bsg_w]; pd.compute_dcl = bsg_dyn->new_J[bsg_w];
-  grad_norms_kernel_body<WITH_DIAG>((int)blockIdx.x, a.bsg_grid, a.nb, (const int*)a.xoff, (const int*)a.toff, (const unsigned char*)a.size, (const unsigned char*)a.manifold, (const double*)a.x, (const double*)a.grad, (double*)a.gpart, pd);
+  grad_norms_kernel_body<WITH_DIAG>((int)blockIdx.x, a.bsg_grid, a.nb, generic(a.xoff), generic(a.toff), generic(a.size), generic(a.manifold), generic(a.x), generic(a.grad), generic(a.gpart), pd);
 }
 
 void launch_grad_norms(hipStream_t s, int nb, const int* blk_xoff, const int* blk_toff, const unsigned char* blk_size,
@@ -160,35 +147,24 @@ __global__ __launch_bounds__(1024) void final_reduce_kernel(const ReduceEntry* _
   final_reduce_kernel_body((int)blockIdx.x, (int)gridDim.x, entries, n_entries, n_slots, scal, host_scal, counter, seq);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
-struct final_reduce_kernel_Args {
+template <template <class> class P>
+struct final_reduce_kernel_ArgsT {
   int bsg_grid;
-  const ReduceEntry* entries;
+  P<const ReduceEntry> entries;
   int n_entries;
   int n_slots;
-  double* scal;
-  double* host_scal;
-  int* counter;
+  P<double> scal;
+  P<double> host_scal;
+  P<int> counter;
   double seq;
 };
-// (the same entry as the kernel reads it: its pointers are GLOBAL pointers — read as generic ones every load through them would be a FLAT
-// instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic)
-struct final_reduce_kernel_ArgsG {
-  int bsg_grid;
-  const ReduceEntry __attribute__((address_space(1)))* entries;
-  int n_entries;
-  int n_slots;
-  double __attribute__((address_space(1)))* scal;
-  double __attribute__((address_space(1)))* host_scal;
-  int __attribute__((address_space(1)))* counter;
-  double seq;
-};
-static_assert(sizeof(final_reduce_kernel_ArgsG) == sizeof(final_reduce_kernel_Args), "layout");
+using final_reduce_kernel_Args = final_reduce_kernel_ArgsT<AsPassed>;
 
 __global__ __launch_bounds__(1024) void final_reduce_kernel_batch(const final_reduce_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list) {
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.y];
-  const final_reduce_kernel_ArgsG& a = reinterpret_cast<const final_reduce_kernel_ArgsG*>(bsg_A)[bsg_w];
+  const final_reduce_kernel_ArgsT<AsRead>& a = batch_entry(bsg_A, bsg_w);
   if ((int)blockIdx.x >= a.bsg_grid) return;
-  final_reduce_kernel_body((int)blockIdx.x, a.bsg_grid, (const ReduceEntry*)a.entries, a.n_entries, a.n_slots, (double*)a.scal, (double*)a.host_scal, (int*)a.counter, bsg_dyn->seq[bsg_w]);
+  final_reduce_kernel_body((int)blockIdx.x, a.bsg_grid, generic(a.entries), a.n_entries, a.n_slots, generic(a.scal), generic(a.host_scal), generic(a.counter), bsg_dyn->seq[bsg_w]);
 }
 void launch_final_reduce(hipStream_t s, const ReduceEntry* entries, int n_entries, int n_slots, double* scal, double* host_scal, int* counter,
                          double seq) {
@@ -295,29 +271,21 @@ __global__ __launch_bounds__(256) void copy_kernel(const double* __restrict__ sr
   copy_kernel_body((int)blockIdx.x, (int)gridDim.x, src, dst, n, nzero_after);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
-struct copy_kernel_Args {
+template <template <class> class P>
+struct copy_kernel_ArgsT {
   int bsg_grid;
-  const double* src;
-  double* dst;
+  P<const double> src;
+  P<double> dst;
   int64_t n;
   int nzero_after;
 };
-// (the same entry as the kernel reads it: its pointers are GLOBAL pointers — read as generic ones every load through them would be a FLAT
-// instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic)
-struct copy_kernel_ArgsG {
-  int bsg_grid;
-  const double __attribute__((address_space(1)))* src;
-  double __attribute__((address_space(1)))* dst;
-  int64_t n;
-  int nzero_after;
-};
-static_assert(sizeof(copy_kernel_ArgsG) == sizeof(copy_kernel_Args), "layout");
+using copy_kernel_Args = copy_kernel_ArgsT<AsPassed>;
 
 __global__ __launch_bounds__(256) void copy_kernel_batch(const copy_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list) {
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.y];
-  const copy_kernel_ArgsG& a = reinterpret_cast<const copy_kernel_ArgsG*>(bsg_A)[bsg_w];
+  const copy_kernel_ArgsT<AsRead>& a = batch_entry(bsg_A, bsg_w);
   if ((int)blockIdx.x >= a.bsg_grid) return;
-  copy_kernel_body((int)blockIdx.x, a.bsg_grid, (const double*)a.src, (double*)a.dst, a.n, a.nzero_after);
+  copy_kernel_body((int)blockIdx.x, a.bsg_grid, generic(a.src), generic(a.dst), a.n, a.nzero_after);
 }
 // ---- the same launches over several windows (bsgpu_batch.cpp)
 void batchargs_grad_norms_pose_diag(BatchArgTable& t, int nb, const int* blk_xoff, const int* blk_toff, const unsigned char* blk_size,

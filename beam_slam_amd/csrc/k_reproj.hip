@@ -212,59 +212,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                        (red.lmd.on && red.lmd.on != 2) ? red.dec : nullptr);   // (lmd.on is 0 or 1; the second test is left from a removed probe mode so that this kernel's code stays what it was)
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
-struct landmark_kernel_Args {
+template <template <class> class P>
+struct landmark_kernel_ArgsT {
   int bsg_grid;
   int n_lm;
-  const int* lm_start;
-  const double* JB;
-  const double2* r;
+  P<const int> lm_start;
+  P<const double> JB;
+  P<const double2> r;
   int n_pose;
-  const double* radius_ptr;
+  P<const double> radius_ptr;
   int compute_scale;
   int compute_dcl;
   int jacobi;
   double lm_lo;
   double lm_hi;
-  double* scale;
-  double* dcl;
-  double* grad;
-  double* Linv_out;
-  double* z_out;
-  double* CR;
+  P<double> scale;
+  P<double> dcl;
+  P<double> grad;
+  P<double> Linv_out;
+  P<double> z_out;
+  P<double> CR;
   int lm_blocks;
   ZeroStep zs;
   double radius_val;
 };
-// (the same entry as the kernel reads it: its pointers are GLOBAL pointers — read as generic ones every load through them would be a FLAT
-// instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic)
-struct landmark_kernel_ArgsG {
-  int bsg_grid;
-  int n_lm;
-  const int __attribute__((address_space(1)))* lm_start;
-  const double __attribute__((address_space(1)))* JB;
-  const double2 __attribute__((address_space(1)))* r;
-  int n_pose;
-  const double __attribute__((address_space(1)))* radius_ptr;
-  int compute_scale;
-  int compute_dcl;
-  int jacobi;
-  double lm_lo;
-  double lm_hi;
-  double __attribute__((address_space(1)))* scale;
-  double __attribute__((address_space(1)))* dcl;
-  double __attribute__((address_space(1)))* grad;
-  double __attribute__((address_space(1)))* Linv_out;
-  double __attribute__((address_space(1)))* z_out;
-  double __attribute__((address_space(1)))* CR;
-  int lm_blocks;
-  ZeroStep zs;
-  double radius_val;
-};
-static_assert(sizeof(landmark_kernel_ArgsG) == sizeof(landmark_kernel_Args), "layout");
+using landmark_kernel_Args = landmark_kernel_ArgsT<AsPassed>;
 
 __global__ __launch_bounds__(256) void landmark_kernel_batch(const landmark_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list) {
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.y];
-  const landmark_kernel_ArgsG& a = reinterpret_cast<const landmark_kernel_ArgsG*>(bsg_A)[bsg_w];
+  const landmark_kernel_ArgsT<AsRead>& a = batch_entry(bsg_A, bsg_w);
   if ((int)blockIdx.x >= a.bsg_grid) return;
   // what changes from iteration to iteration: the radius, whether the Jacobi scale / LM diagonal are (re)computed, what the step's clearing covers
   const double radius_val = bsg_dyn->radius[bsg_w];
@@ -272,7 +248,7 @@ __global__ __launch_bounds__(256) void landmark_kernel_batch(const landmark_kern
   ZeroStep zs = a.zs;
   zs.radius = radius_val;
   if (!compute_dcl) { zs.c += SC_CHOL_FAIL - SC_GRAD_MAX; zs.nc = 1; }
-  landmark_kernel_body((int)blockIdx.x, a.bsg_grid, a.n_lm, (const int*)a.lm_start, (const double*)a.JB, (const double2*)a.r, a.n_pose, nullptr, compute_scale, compute_dcl, a.jacobi, a.lm_lo, a.lm_hi, (double*)a.scale, (double*)a.dcl, (double*)a.grad, (double*)a.Linv_out, (double*)a.z_out, (double*)a.CR, a.lm_blocks, zs, radius_val);
+  landmark_kernel_body((int)blockIdx.x, a.bsg_grid, a.n_lm, generic(a.lm_start), generic(a.JB), generic(a.r), a.n_pose, nullptr, compute_scale, compute_dcl, a.jacobi, a.lm_lo, a.lm_hi, generic(a.scale), generic(a.dcl), generic(a.grad), generic(a.Linv_out), generic(a.z_out), generic(a.CR), a.lm_blocks, zs, radius_val);
 }
 
 // factors whose landmark is constant: C = 0, rho = r
@@ -288,29 +264,21 @@ __global__ void landmark_tail_kernel(int first, int n, const double2* __restrict
   landmark_tail_kernel_body((int)blockIdx.x, (int)gridDim.x, first, n, r, CR);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
-struct landmark_tail_kernel_Args {
+template <template <class> class P>
+struct landmark_tail_kernel_ArgsT {
   int bsg_grid;
   int first;
   int n;
-  const double2* r;
-  double* CR;
+  P<const double2> r;
+  P<double> CR;
 };
-// (the same entry as the kernel reads it: its pointers are GLOBAL pointers — read as generic ones every load through them would be a FLAT
-// instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic)
-struct landmark_tail_kernel_ArgsG {
-  int bsg_grid;
-  int first;
-  int n;
-  const double2 __attribute__((address_space(1)))* r;
-  double __attribute__((address_space(1)))* CR;
-};
-static_assert(sizeof(landmark_tail_kernel_ArgsG) == sizeof(landmark_tail_kernel_Args), "layout");
+using landmark_tail_kernel_Args = landmark_tail_kernel_ArgsT<AsPassed>;
 
 __global__ void landmark_tail_kernel_batch(const landmark_tail_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list) {
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.y];
-  const landmark_tail_kernel_ArgsG& a = reinterpret_cast<const landmark_tail_kernel_ArgsG*>(bsg_A)[bsg_w];
+  const landmark_tail_kernel_ArgsT<AsRead>& a = batch_entry(bsg_A, bsg_w);
   if ((int)blockIdx.x >= a.bsg_grid) return;
-  landmark_tail_kernel_body((int)blockIdx.x, a.bsg_grid, a.first, a.n, (const double2*)a.r, (double*)a.CR);
+  landmark_tail_kernel_body((int)blockIdx.x, a.bsg_grid, a.first, a.n, generic(a.r), generic(a.CR));
 }
 
 void launch_landmark(hipStream_t s, const Visual& v, int n_pose, const double* radius_ptr, int compute_scale,
@@ -494,63 +462,38 @@ __global__ __launch_bounds__(64) void pairs_kernel(int n_seg, const int* __restr
   pairs_kernel_body((int)blockIdx.x, (int)gridDim.x, n_seg, seg_ci, seg_cj, seg_start, ent_fa, ent_fb, J, r, CR, cp_tq, cp_tp, S, ld, rhs_row, grad, hdiag, perm, grad_only, n_pair_blocks, small, n_small_units);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
-struct pairs_kernel_Args {
+template <template <class> class P>
+struct pairs_kernel_ArgsT {
   int bsg_grid;
   int n_seg;
-  const int* seg_ci;
-  const int* seg_cj;
-  const int* seg_start;
-  const int* ent_fa;
-  const int* ent_fb;
-  const double* J;
-  const double2* r;
-  const double* CR;
-  const int* cp_tq;
-  const int* cp_tp;
-  double* S;
+  P<const int> seg_ci;
+  P<const int> seg_cj;
+  P<const int> seg_start;
+  P<const int> ent_fa;
+  P<const int> ent_fb;
+  P<const double> J;
+  P<const double2> r;
+  P<const double> CR;
+  P<const int> cp_tq;
+  P<const int> cp_tp;
+  P<double> S;
   int ld;
   int rhs_row;
-  double* grad;
-  double* hdiag;
-  const int* perm;
+  P<double> grad;
+  P<double> hdiag;
+  P<const int> perm;
   int grad_only;
   int n_pair_blocks;
   SmallGroupSet small;
   int n_small_units;
 };
-// (the same entry as the kernel reads it: its pointers are GLOBAL pointers — read as generic ones every load through them would be a FLAT
-// instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic)
-struct pairs_kernel_ArgsG {
-  int bsg_grid;
-  int n_seg;
-  const int __attribute__((address_space(1)))* seg_ci;
-  const int __attribute__((address_space(1)))* seg_cj;
-  const int __attribute__((address_space(1)))* seg_start;
-  const int __attribute__((address_space(1)))* ent_fa;
-  const int __attribute__((address_space(1)))* ent_fb;
-  const double __attribute__((address_space(1)))* J;
-  const double2 __attribute__((address_space(1)))* r;
-  const double __attribute__((address_space(1)))* CR;
-  const int __attribute__((address_space(1)))* cp_tq;
-  const int __attribute__((address_space(1)))* cp_tp;
-  double __attribute__((address_space(1)))* S;
-  int ld;
-  int rhs_row;
-  double __attribute__((address_space(1)))* grad;
-  double __attribute__((address_space(1)))* hdiag;
-  const int __attribute__((address_space(1)))* perm;
-  int grad_only;
-  int n_pair_blocks;
-  SmallGroupSet small;
-  int n_small_units;
-};
-static_assert(sizeof(pairs_kernel_ArgsG) == sizeof(pairs_kernel_Args), "layout");
+using pairs_kernel_Args = pairs_kernel_ArgsT<AsPassed>;
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) void pairs_kernel_batch(const pairs_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list) {
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.y];
-  const pairs_kernel_ArgsG& a = reinterpret_cast<const pairs_kernel_ArgsG*>(bsg_A)[bsg_w];
+  const pairs_kernel_ArgsT<AsRead>& a = batch_entry(bsg_A, bsg_w);
   if ((int)blockIdx.x >= a.bsg_grid) return;
-  pairs_kernel_body((int)blockIdx.x, a.bsg_grid, a.n_seg, (const int*)a.seg_ci, (const int*)a.seg_cj, (const int*)a.seg_start, (const int*)a.ent_fa, (const int*)a.ent_fb, (const double*)a.J, (const double2*)a.r, (double*)a.CR, (const int*)a.cp_tq, (const int*)a.cp_tp, (double*)a.S, a.ld, a.rhs_row, (double*)a.grad, (double*)a.hdiag, (const int*)a.perm, bsg_dyn->grad_only[bsg_w], a.n_pair_blocks, a.small, a.n_small_units);
+  pairs_kernel_body((int)blockIdx.x, a.bsg_grid, a.n_seg, generic(a.seg_ci), generic(a.seg_cj), generic(a.seg_start), generic(a.ent_fa), generic(a.ent_fb), generic(a.J), generic(a.r), generic(a.CR), generic(a.cp_tq), generic(a.cp_tp), generic(a.S), a.ld, a.rhs_row, generic(a.grad), generic(a.hdiag), generic(a.perm), bsg_dyn->grad_only[bsg_w], a.n_pair_blocks, a.small, a.n_small_units);
 }
 
 constexpr size_t kPairsLds = sizeof(double2) * 64 * (6 + 6 + 4 + 3) + sizeof(int) * 128;
@@ -820,65 +763,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   backsub_mcc_kernel_body((int)blockIdx.x, (int)gridDim.x, n_lm, n_lm_groups, n_elim, n, lm_start, J, ja, JB, r, CR, fac_t, Linv, z, n_pose, y_pose, y_lds, delta, mcc_part, n_vis_blocks, small, n_small_units, up, first_update_block);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
-struct backsub_mcc_kernel_Args {
+template <template <class> class P>
+struct backsub_mcc_kernel_ArgsT {
   int bsg_grid;
   int n_lm;
   int n_lm_groups;
   int n_elim;
   int n;
-  const int* lm_start;
-  const double* J;
+  P<const int> lm_start;
+  P<const double> J;
   int ja;
-  const double* JB;
-  const double2* r;
-  const double* CR;
-  const int2* fac_t;
-  const double* Linv;
-  const double* z;
+  P<const double> JB;
+  P<const double2> r;
+  P<const double> CR;
+  P<const int2> fac_t;
+  P<const double> Linv;
+  P<const double> z;
   int n_pose;
-  const double* y_pose;
-  double* delta;
-  double* mcc_part;
+  P<const double> y_pose;
+  P<double> delta;
+  P<double> mcc_part;
   int n_vis_blocks;
   SmallGroupSet small;
   int n_small_units;
   UpdateRide up;
   int first_update_block;
 };
-// (the same entry as the kernel reads it: its pointers are GLOBAL pointers — read as generic ones every load through them would be a FLAT
-// instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic)
-struct backsub_mcc_kernel_ArgsG {
-  int bsg_grid;
-  int n_lm;
-  int n_lm_groups;
-  int n_elim;
-  int n;
-  const int __attribute__((address_space(1)))* lm_start;
-  const double __attribute__((address_space(1)))* J;
-  int ja;
-  const double __attribute__((address_space(1)))* JB;
-  const double2 __attribute__((address_space(1)))* r;
-  const double __attribute__((address_space(1)))* CR;
-  const int2 __attribute__((address_space(1)))* fac_t;
-  const double __attribute__((address_space(1)))* Linv;
-  const double __attribute__((address_space(1)))* z;
-  int n_pose;
-  const double __attribute__((address_space(1)))* y_pose;
-  double __attribute__((address_space(1)))* delta;
-  double __attribute__((address_space(1)))* mcc_part;
-  int n_vis_blocks;
-  SmallGroupSet small;
-  int n_small_units;
-  UpdateRide up;
-  int first_update_block;
-};
-static_assert(sizeof(backsub_mcc_kernel_ArgsG) == sizeof(backsub_mcc_kernel_Args), "layout");
+using backsub_mcc_kernel_Args = backsub_mcc_kernel_ArgsT<AsPassed>;
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void backsub_mcc_kernel_batch(const backsub_mcc_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list, int bsg_y_lds) {
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.y];
-  const backsub_mcc_kernel_ArgsG& a = reinterpret_cast<const backsub_mcc_kernel_ArgsG*>(bsg_A)[bsg_w];
+  const backsub_mcc_kernel_ArgsT<AsRead>& a = batch_entry(bsg_A, bsg_w);
   if ((int)blockIdx.x >= a.bsg_grid) return;
-  backsub_mcc_kernel_body((int)blockIdx.x, a.bsg_grid, a.n_lm, a.n_lm_groups, a.n_elim, a.n, (const int*)a.lm_start, (const double*)a.J, a.ja, (const double*)a.JB, (const double2*)a.r, (double*)a.CR, (const int2*)a.fac_t, (const double*)a.Linv, (const double*)a.z, a.n_pose, (const double*)a.y_pose, bsg_y_lds, (double*)a.delta, (double*)a.mcc_part, a.n_vis_blocks, a.small, a.n_small_units, a.up, a.first_update_block);
+  backsub_mcc_kernel_body((int)blockIdx.x, a.bsg_grid, a.n_lm, a.n_lm_groups, a.n_elim, a.n, generic(a.lm_start), generic(a.J), a.ja, generic(a.JB), generic(a.r), generic(a.CR), generic(a.fac_t), generic(a.Linv), generic(a.z), a.n_pose, generic(a.y_pose), bsg_y_lds, generic(a.delta), generic(a.mcc_part), a.n_vis_blocks, a.small, a.n_small_units, a.up, a.first_update_block);
 }
 
 // ---- the same launches over several windows (bsgpu_batch.cpp): one table entry per window, grids as the lone launches compute them

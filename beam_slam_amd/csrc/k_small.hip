@@ -439,58 +439,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) voi
   visual_imu_eval_kernel_body<true>((int)blockIdx.x - n_units, (int)gridDim.x - n_units, delta, prior, part_delta, part_prior, n_imu_blocks, n, fac, pix, wgt, x, cams, losses, r_out, J_out, ja, JB_out, cost_part, count_inactive);
 }
 // one launch over several windows (bsgpu_batch.cpp): blockIdx.y picks the window of list `bsg_list`, its arguments come from memory
-struct visual_imu_eval_kernel_Args {
+template <template <class> class P>
+struct visual_imu_eval_kernel_ArgsT {
   int bsg_grid;
   SmallGroup delta;
   SmallGroup prior;
-  double* part_delta;
-  double* part_prior;
+  P<double> part_delta;
+  P<double> part_prior;
   int n_imu_blocks;
   int n;
-  const int4* fac;
-  const double2* pix;
-  const double* wgt;
-  const double* x;
-  const DevCamera* cams;
-  const DevLoss* losses;
-  double2* r_out;
-  double* J_out;
+  P<const int4> fac;
+  P<const double2> pix;
+  P<const double> wgt;
+  P<const double> x;
+  P<const DevCamera> cams;
+  P<const DevLoss> losses;
+  P<double2> r_out;
+  P<double> J_out;
   int ja;
-  double* JB_out;
-  double* cost_part;
+  P<double> JB_out;
+  P<double> cost_part;
   int count_inactive;
 };
-// (the same entry as the kernel reads it: its pointers are GLOBAL pointers — read as generic ones every load through them would be a FLAT
-// instruction, which also counts against the LDS counter and serialises the kernels that overlap gathers with LDS traffic)
-struct visual_imu_eval_kernel_ArgsG {
-  int bsg_grid;
-  SmallGroup delta;
-  SmallGroup prior;
-  double __attribute__((address_space(1)))* part_delta;
-  double __attribute__((address_space(1)))* part_prior;
-  int n_imu_blocks;
-  int n;
-  const int4 __attribute__((address_space(1)))* fac;
-  const double2 __attribute__((address_space(1)))* pix;
-  const double __attribute__((address_space(1)))* wgt;
-  const double __attribute__((address_space(1)))* x;
-  const DevCamera __attribute__((address_space(1)))* cams;
-  const DevLoss __attribute__((address_space(1)))* losses;
-  double2 __attribute__((address_space(1)))* r_out;
-  double __attribute__((address_space(1)))* J_out;
-  int ja;
-  double __attribute__((address_space(1)))* JB_out;
-  double __attribute__((address_space(1)))* cost_part;
-  int count_inactive;
-};
-static_assert(sizeof(visual_imu_eval_kernel_ArgsG) == sizeof(visual_imu_eval_kernel_Args), "layout");
+using visual_imu_eval_kernel_Args = visual_imu_eval_kernel_ArgsT<AsPassed>;
 
 template <bool WITH_J>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 4))) void visual_imu_eval_kernel_batch(const visual_imu_eval_kernel_Args* __restrict__ bsg_A, const BatchDyn* __restrict__ bsg_dyn, int bsg_list) {
   const int bsg_w = bsg_dyn->idx[bsg_list][blockIdx.y];
-  const visual_imu_eval_kernel_ArgsG& a = reinterpret_cast<const visual_imu_eval_kernel_ArgsG*>(bsg_A)[bsg_w];
+  const visual_imu_eval_kernel_ArgsT<AsRead>& a = batch_entry(bsg_A, bsg_w);
   if ((int)blockIdx.x >= a.bsg_grid) return;
-  visual_imu_eval_kernel_body<WITH_J>((int)blockIdx.x, a.bsg_grid, a.delta, a.prior, (double*)a.part_delta, (double*)a.part_prior, a.n_imu_blocks, a.n, (const int4*)a.fac, (const double2*)a.pix, (const double*)a.wgt, (const double*)a.x, (const DevCamera*)a.cams, (const DevLoss*)a.losses, (double2*)a.r_out, (double*)a.J_out, a.ja, (double*)a.JB_out, (double*)a.cost_part, a.count_inactive);
+  visual_imu_eval_kernel_body<WITH_J>((int)blockIdx.x, a.bsg_grid, a.delta, a.prior, generic(a.part_delta), generic(a.part_prior), a.n_imu_blocks, a.n, generic(a.fac), generic(a.pix), generic(a.wgt), generic(a.x), generic(a.cams), generic(a.losses), generic(a.r_out), generic(a.J_out), a.ja, generic(a.JB_out), generic(a.cost_part), a.count_inactive);
 }
 void launch_visual_imu_eval(hipStream_t s, const Visual& v, const SmallGroup& delta, const SmallGroup& prior, const double* x, const DevCamera* cams,
                             const DevLoss* losses, bool with_J, double* cost_part_vis, double* part_delta, double* part_prior, const ReduceRide* red) {
